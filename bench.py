@@ -1,7 +1,13 @@
 """Headline benchmark: diff-ICP PSR iterations/sec on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
                     [--workload two_set_100k|two_set_100k_2d|two_set_50k|two_set_200k|two_set_50k_exact|atlas_c4|atlas_c4_fixed|c5|c5_alt]
+    (A plain run sets up, warms up, times the K steps and prints the line.  --full adds what
+     takes runs of its own after the timed region: the "cpu_baseline" object, the
+     "kernel_sum_100k*" probes and, for concurrent atlas frames, the per-kernel accounting
+     from one extra sequential-frame iteration.  --dump-outputs DIR writes the state the last
+     timed step left -- warped points, GMM targets, momenta, GMM parameters, free energy --
+     as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.)
     (N > 1: one rank per GPU over RCCL.  Under torch.distributed.run WORLD_SIZE must equal N;
      started without it, bench.py starts `python -m torch.distributed.run --nproc-per-node N`
      on itself as a child process -- before anything touches the GPU -- and exits with the
@@ -19,8 +25,8 @@ c5_alt keep the frames per rank fixed (weak scaling), atlas_c4_fixed keeps the w
 
 Rank 0 prints ONE JSON line (value = iterations of all ranks / max-over-ranks time) with a
 "roofline" object for the dominant kernel (algorithmic flop per launch / average launch
-time from HIP events on the launch stream, vs the 157.3 TFLOP/s fp32 peak) and a
-"cpu_baseline" object (the oracle's C restatement timed on this host on a bounded sample,
+time from HIP events on the launch stream, vs the 157.3 TFLOP/s fp32 peak) and, with --full,
+a "cpu_baseline" object (the oracle's C restatement timed on this host on a bounded sample,
 extrapolated to one iteration of the same workload from the live pair counts).
 
 Two-set workloads at N > 1 row-split the ONE match over the ranks by default (SURVEY f1,
@@ -281,6 +287,57 @@ def load_issue(kernel_name):
         return None, None
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def timed_outputs(psr):
+    """{name: tensor}: what the last PSR iteration left for its caller -- per local frame k the
+    warped points x1 and GMM targets y of every structure s and the momenta a0, per structure
+    the GMM's mu / w / sigma, and the free energy with its regularisation and data terms."""
+    out = {}
+    for k in psr.frames:
+        for s in range(psr.S):
+            out[f"x1_k{k}_s{s}"] = psr.x1[k, s]
+            out[f"y_k{k}_s{s}"] = psr.y[k, s]
+        out[f"a0_k{k}"] = psr.a0[k]
+    for s, g in enumerate(psr.GMMi):
+        out[f"gmm_mu_s{s}"] = g.mu
+        out[f"gmm_w_s{s}"] = g.w
+        out[f"gmm_sigma_s{s}"] = torch.tensor([float(g.sigma)], dtype=torch.float64)
+    out["FE"] = torch.tensor([float(psr.FE)], dtype=torch.float64)
+    out["regloss"] = torch.tensor([float(psr.regloss[k]) for k in psr.frames], dtype=torch.float64)
+    out["quadloss"] = torch.tensor([[float(psr.quadloss[k, s]) for s in range(psr.S)]
+                                    for k in psr.frames], dtype=torch.float64)
+    return out
+
+
+def dump_outputs(psr, path, rank=0, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: timed_outputs(psr) as path/<name>.npy (float32; the scalars float64).
+    Above `budget` bytes in all, the point arrays keep a fixed seeded sample of their rows
+    (the same rows in every run, in order).  Ranks write their own frames' arrays; the GMM
+    parameters and the energies, identical on all ranks, come from rank 0."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for name, t in timed_outputs(psr).items():
+        if rank != 0 and not name[:3] in ("x1_", "y_k", "a0_"):
+            continue
+        t = t.detach().cpu()
+        arrays[name] = t.numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        keep = 0.95 * budget / total
+        g = torch.Generator().manual_seed(0)
+        for name in sorted(arrays):
+            a = arrays[name]
+            if a.ndim == 2 and a.shape[0] > 1024:
+                idx = torch.randperm(a.shape[0], generator=g)[:max(1, int(a.shape[0] * keep))]
+                arrays[name] = a[idx.sort().values.numpy()]
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    return sum(a.nbytes for a in arrays.values())
+
+
 def launch_plan(argv, env):
     """How `bench.py argv` runs, decided before any GPU call: ("run", world) in this process
     (world 1, or a rank started by torch.distributed.run with WORLD_SIZE = --gpus), or
@@ -340,7 +397,13 @@ def _main(out):
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="two_set_100k", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own after the timed steps: the CPU baseline, "
+                         "the 100k kernel-sum probes, and for concurrent atlas frames the extra "
+                         "sequential-frame iteration behind the per-kernel figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-profile", action="store_true", help="skip live per-kernel events")
     ap.add_argument("--concurrent-frames", type=int, default=None,
                     help="atlas workloads: frames optimised concurrently (host threads / HIP "
@@ -359,6 +422,8 @@ def _main(out):
                     help="two-set workloads at N > 1: N independent replicas (weak scaling) "
                          "instead of row-splitting the one match over the N GPUs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = launch_plan(sys.argv[1:], os.environ)[1]
     rank = int(os.environ.get("RANK", "0"))
@@ -489,7 +554,11 @@ def _main(out):
         dist.all_gather_object(ranks, mine)
     else:
         ranks = [mine]
-    if prof is not None and concurrent:
+    if args.dump_outputs:
+        # before anything below runs the workload again: the state the last timed step left
+        nbytes = dump_outputs(psr, args.dump_outputs, rank, DUMP_BUDGET_BYTES // world)
+        log(f"[rank {rank}] wrote {nbytes / 1e6:.1f} MB of outputs to {args.dump_outputs}")
+    if prof is not None and concurrent and args.full:
         # the frames one after another, with the kernel geometry the timed (concurrent)
         # iterations used (batch_share 0 = the concurrent frames): the same kernels, timed alone
         saved = psr.concurrent_frames, psr.batch_share
@@ -600,13 +669,13 @@ def _main(out):
                     roof["frac_executed_at_eff_clock"] = round(
                         achieved * efpp / fpp / (FP32_PEAK_TFLOPS * clk / 2.4), 4)
         base = None
-        if not args.no_cpu_baseline and world == 1 and pair_counts:
+        if args.full and not args.no_cpu_baseline and world == 1 and pair_counts:
             try:
                 base = cpu_baseline(pair_counts, min(wl["N"], 50000), D=wl.get("D", 3))
             except Exception as e:  # baseline is informative; never fail the bench on it
                 base = {"error": repr(e)}
         ksum = ksum_xy = None
-        if world == 1 and wl.get("N") == 100000 and wl.get("D", 3) == 3:
+        if args.full and world == 1 and wl.get("N") == 100000 and wl.get("D", 3) == 3:
             try:
                 ksum = kernel_sum_probe(dev, wl["N"])
                 ksum_xy = kernel_sum_probe(dev, wl["N"], same=False)
@@ -632,7 +701,7 @@ def _main(out):
                             "kernel_busy_s = summed kernel time (timed iterations only; absent when frames run concurrently, whose per-launch event times overlap)"}
         line = {
             "metric": METRIC, "value": round(value, 5), "unit": "PSR iterations/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
             "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": cfg, "roofline": roof, "cpu_baseline": base,

@@ -97,6 +97,66 @@ def test_launch_plan_rank_under_torchrun_and_world_mismatch():
         b.launch_plan([], {"WORLD_SIZE": "2"})
 
 
+class _StubPSR:
+    """The attributes bench.timed_outputs reads, as DiffPSR holds them after an iteration."""
+
+    def __init__(self, K=2, S=2, N=3000, C=16, D=3):
+        import types
+
+        import numpy as np
+        import torch
+        g = torch.Generator().manual_seed(3)
+        self.frames, self.S = list(range(K)), S
+        self.x1 = np.empty((K, S), dtype=object)
+        self.y = np.empty((K, S), dtype=object)
+        for k in range(K):
+            for s in range(S):
+                self.x1[k, s] = torch.rand(N, D, generator=g)
+                self.y[k, s] = torch.rand(N, D, generator=g)
+        self.a0 = [torch.rand(S * N, D, generator=g) for _ in range(K)]
+        self.GMMi = [types.SimpleNamespace(mu=torch.rand(C, D, generator=g), w=torch.zeros(C), sigma=0.05 + s)
+                     for s in range(S)]
+        self.FE, self.regloss, self.quadloss = 1.5, [0.25] * K, np.ones((K, S))
+
+
+def test_dump_outputs_writes_every_array(tmp_path):
+    import numpy as np
+    b = _bench()
+    psr = _StubPSR()
+    n = b.dump_outputs(psr, str(tmp_path / "o"))
+    want = b.timed_outputs(psr)
+    files = sorted(p.name for p in (tmp_path / "o").iterdir())
+    assert files == sorted(k + ".npy" for k in want)
+    assert n == sum(np.load(tmp_path / "o" / f).nbytes for f in files)
+    for k, t in want.items():
+        a = np.load(tmp_path / "o" / (k + ".npy"))
+        assert a.dtype in (np.float32, np.float64)
+        assert np.array_equal(a, t.numpy())
+    assert float(np.load(tmp_path / "o" / "gmm_sigma_s1.npy")[0]) == 1.05
+
+
+def test_dump_outputs_over_budget_keeps_a_fixed_row_sample(tmp_path):
+    import numpy as np
+    b = _bench()
+    psr = _StubPSR()
+    budget = 100_000
+    n1 = b.dump_outputs(psr, str(tmp_path / "a"), budget=budget)
+    n2 = b.dump_outputs(psr, str(tmp_path / "b"), budget=budget)
+    assert n1 == n2 <= budget
+    x_full = psr.x1[1, 0].numpy()
+    for name in sorted(p.name for p in (tmp_path / "a").iterdir()):
+        a, a2 = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert np.array_equal(a, a2), name          # the same rows in every run
+    x = np.load(tmp_path / "a" / "x1_k1_s0.npy")
+    assert 0 < x.shape[0] < x_full.shape[0] and x.shape[1] == 3
+    # every kept row is a row of the full array, in its order
+    rows = {r.tobytes(): i for i, r in enumerate(x_full)}
+    idx = [rows[r.tobytes()] for r in x]
+    assert idx == sorted(idx)
+    # the small arrays stay whole
+    assert np.load(tmp_path / "a" / "gmm_mu_s0.npy").shape == (16, 3)
+
+
 def test_two_set_2d_workload_is_declared():
     b = _bench()
     wl = b.WORKLOADS["two_set_100k_2d"]
