@@ -72,6 +72,12 @@ _SIGNATURES = {
                                              _P, _P, _P, _P, _SZ, _P],
     "dicp_lddmm_ode_self_bwd_part_zs_f32": [_P, _P, _P, _P, _P, _I64, _INT, _DBL, _DBL, _INT, _INT, _P,
                                             _I64, _I64, _P, _P, _P, _SZ, _P],
+    "dicp_pair_boxes_f32": [_P, _I64, _INT, _DBL, _P, _P],
+    "dicp_lddmm_ode_self_fwd_box_f32": [_P, _P, _I64, _INT, _DBL, _DBL, _P, _P, _P, _P, _P, _P, _SZ, _P],
+    "dicp_lddmm_euler_step_box_f32": [_P, _P, _I64, _INT, _DBL, _DBL, _DBL, _P, _P, _P, _P, _P, _P, _P,
+                                      _SZ, _P],
+    "dicp_lddmm_euler_adjoint_step_box_f32": [_P, _P, _P, _P, _P, _I64, _INT, _DBL, _DBL, _DBL, _P, _P,
+                                              _P, _P, _P, _P, _P, _SZ, _P],
     "dicp_gauss_red_grad_f32": [_INT, _P, _I64, _P, _I64, _INT, _P, _P, _P, _P, _P, _DBL, _P, _P, _SZ, _P],
     "dicp_kernel_ridge_cg_f32": [_P, _I64, _INT, _DBL, _DBL, _DBL, _P, _P, _INT, _INT, _P, _SZ, _P],
     "dicp_workspace_bytes": [_INT, _I64, _I64, _INT],
@@ -572,18 +578,81 @@ def ode_self_fwd(q, p, sigma: float, eta: float, want_div: bool, want_h: bool = 
     return v, mG, g, h
 
 
+# ---- Gaussian cutoff of far tile pairs (dicp_pair_boxes_f32 and the *_box_f32 steps) ----
+CUT_TILE = 64          # points per box (csrc/lddmm_sym.hpp kCutTile)
+CUT_MIN_M = 32768      # option pair_cutoff = 1: shootings from this many support points
+# calls of the *_box_f32 entries with boxes (which path a shooting took: tests/test_gpu_pair_cutoff.py)
+CUT_CALLS = {"fwd": 0, "step": 0, "adjoint": 0}
+
+
+def pair_boxes(q, sigma: float, out=None):
+    """Boxes of q (M, D) for the *_box_f32 steps: (ceil(M / 64), 2 D), lo then hi per sub-tile of
+    64 consecutive points, in the kernels' scaled coordinates (dicp_pair_boxes_f32)."""
+    q = _dev(q, "q")
+    M, D = q.shape
+    nB = (M + CUT_TILE - 1) // CUT_TILE
+    if out is None:
+        out = torch.empty((nB, 2 * D), device=q.device, dtype=torch.float32)
+    elif not out.is_contiguous() or tuple(out.shape) != (nB, 2 * D) or out.dtype != torch.float32:
+        raise ValueError(f"boxes must be a contiguous float32 ({nB}, {2 * D}) tensor")
+    if M:
+        _check_rc(lib().dicp_pair_boxes_f32(_ptr(q), M, D, float(sigma), _ptr(out), _stream(q.device)),
+                  "pair_boxes")
+    return out
+
+
+def _boxes(boxes, M, D, dev, name="boxes"):
+    if boxes is None:
+        return None
+    nB = (M + CUT_TILE - 1) // CUT_TILE
+    if (not boxes.is_contiguous() or tuple(boxes.shape) != (nB, 2 * D) or boxes.dtype != torch.float32
+            or boxes.device != dev):
+        raise ValueError(f"{name} must be a contiguous float32 ({nB}, {2 * D}) tensor on {dev}")
+    return boxes
+
+
+def ode_self_fwd_box(q, p, sigma: float, eta: float, want_div: bool, boxes, zs_out=None):
+    """(v, mG, g rows) of the fused ODE over all rows given the boxes of q
+    (dicp_lddmm_ode_self_fwd_box_f32; boxes=None: the dense pass); zs_out: (M, D) divergence rows."""
+    q = _dev(q, "q")
+    p = _dev(p, "p")
+    M, D = q.shape
+    dev = q.device
+    boxes = _boxes(boxes, M, D, dev)
+    zs_out = _zs_buf(zs_out, M, D, dev)
+    v = torch.empty_like(q)
+    mG = torch.empty_like(q)
+    g = torch.empty(M, device=dev, dtype=torch.float32) if (want_div or eta != 0) else None
+    if M == 0:
+        return v, mG, g
+    ws, nb = _workspace(WS_ODE_SELF_FWD, M, M, D, dev)
+    if boxes is not None:
+        CUT_CALLS["fwd"] += 1
+    rc = _launch(("ode_self_fwd_eta" if eta else "ode_self_fwd"), M * M, 4 * M * (4 * D + 2),
+                 lambda: lib().dicp_lddmm_ode_self_fwd_box_f32(_ptr(q), _ptr(p), M, D, float(sigma), float(eta),
+                                                               _ptr(v), _ptr(mG), _ptr(g), _ptr(zs_out),
+                                                               _ptr(boxes), _ptr(ws), nb, _stream(dev)))
+    _check_rc(rc, "ode_self_fwd_box")
+    return v, mG, g
+
+
 def euler_step(q, p, sigma: float, eta: float, dt: float, want_div: bool, q_out=None, p_out=None,
-               g_out=None, order=None, want_p: bool = True, zs_out=None):
+               g_out=None, order=None, want_p: bool = True, zs_out=None, boxes=None, boxes_out=None):
     """(q + dt v, p + dt mG, g rows or None) in one fused pass (dicp_lddmm_euler_step_ord_f32);
     q_out / p_out / g_out: optional contiguous destinations (must not overlap q, p); order:
     optional int32 row visit order (see ode_self_fwd); want_p=False: (q_next, None, g) -- the
     momentum update is not formed (the packed pass skips the sums that feed mG only);
     zs_out: optional (M, D) destination of the divergence rows (dicp_lddmm_euler_step_zs_f32,
-    eta = 0)."""
+    eta = 0); boxes: the boxes of q (pair_boxes) -- the step then skips far tile pairs
+    (dicp_lddmm_euler_step_box_f32, no row order); boxes_out: destination of q_next's boxes."""
     q = _dev(q, "q")
     p = _dev(p, "p")
     M, D = q.shape
     order = _order(order, M, q.device)
+    boxes = _boxes(boxes, M, D, q.device)
+    boxes_out = _boxes(boxes_out, M, D, q.device, "boxes_out")
+    if (boxes is not None or boxes_out is not None) and order is not None:
+        raise ValueError("euler_step: the box form takes no row order")
     zs_out = _zs_buf(zs_out, M, D, q.device)
     qn = torch.empty_like(q) if q_out is None else q_out
     pn = (torch.empty_like(q) if p_out is None else p_out) if want_p else None
@@ -601,6 +670,15 @@ def euler_step(q, p, sigma: float, eta: float, dt: float, want_div: bool, q_out=
         return qn, pn, g
     ws, nb = _workspace(WS_ODE_SELF_FWD, M, M, D, q.device)
     name = ("ode_self_fwd_eta" if eta else "ode_self_fwd") + ("" if want_p else "_nog")
+    if boxes is not None or boxes_out is not None:
+        if boxes is not None:
+            CUT_CALLS["step"] += 1
+        rc = _launch(name, M * M, 4 * M * (4 * D + 1),
+                     lambda: lib().dicp_lddmm_euler_step_box_f32(
+                         _ptr(q), _ptr(p), M, D, float(sigma), float(eta), float(dt), _ptr(qn), _ptr(pn),
+                         _ptr(g), _ptr(zs_out), _ptr(boxes), _ptr(boxes_out), _ptr(ws), nb, _stream(q.device)))
+        _check_rc(rc, "euler_step_box")
+        return qn, pn, g
     rc = _launch(name, M * M, 4 * M * (4 * D + 1),
                  lambda: lib().dicp_lddmm_euler_step_zs_f32(_ptr(q), _ptr(p), M, 0, M, D, float(sigma),
                                                             float(eta), float(dt), _ptr(order), _ptr(qn),
@@ -611,7 +689,7 @@ def euler_step(q, p, sigma: float, eta: float, dt: float, want_div: bool, q_out=
 
 
 def euler_adjoint_step(q, p, lq, lp, gdiv, sigma: float, eta: float, dt: float, addq=None, addp=None,
-                       want_lq: bool = True, zs=None):
+                       want_lq: bool = True, zs=None, boxes=None):
     """(lq + dt gq + addq, lp + dt gp + addp) with (gq, gp) the ODE VJP for cotangents
     (lq, lp, gdiv) -- one fused pass (dicp_lddmm_euler_adjoint_step_f32).  want_lq=False:
     (None, lp_next) only -- the gq half of the pair algebra is skipped.  lp=None: a zero
@@ -628,12 +706,22 @@ def euler_adjoint_step(q, p, lq, lp, gdiv, sigma: float, eta: float, dt: float, 
     addp = None if addp is None else _dev(addp, "addp")
     M, D = q.shape
     zs = _zs_buf(zs, M, D, q.device, "zs")
+    boxes = _boxes(boxes, M, D, q.device)   # of q: dicp_lddmm_euler_adjoint_step_box_f32
     lqn = torch.empty_like(q) if want_lq else None
     lpn = torch.empty_like(q)
     if M == 0:
         return lqn, lpn
     ws, nb = _workspace(WS_ODE_SELF_BWD, M, M, D, q.device)
     name = _bwd_name(eta, want_lq, lp is None)
+    if boxes is not None:
+        CUT_CALLS["adjoint"] += 1
+        rc = _launch(name, M * M, 4 * M * (8 * D if want_lq else 7 * D),
+                     lambda: lib().dicp_lddmm_euler_adjoint_step_box_f32(
+                         _ptr(q), _ptr(p), _ptr(lq), _ptr(lp), _ptr(gdiv), M, D, float(sigma), float(eta),
+                         float(dt), _ptr(addq), _ptr(addp), _ptr(zs), _ptr(boxes), _ptr(lqn), _ptr(lpn),
+                         _ptr(ws), nb, _stream(q.device)))
+        _check_rc(rc, "euler_adjoint_step_box")
+        return lqn, lpn
     rc = _launch(name, M * M, 4 * M * (8 * D if want_lq else 7 * D),
                  lambda: lib().dicp_lddmm_euler_adjoint_step_zs_f32(
                      _ptr(q), _ptr(p), _ptr(lq), _ptr(lp), _ptr(gdiv), M, D, float(sigma), float(eta),

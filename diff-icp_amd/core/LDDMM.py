@@ -23,7 +23,7 @@ from ..tools.kernel import GaussKernel, SVDpow
 from ..tools.optim import LBFGS_optimization
 from ..tools.spec import defspec, getspec
 from .shooting import (HamiltonianFn, OdeExtFn, OdeFn, RowOrderCache, ShootCache, ShootFn,
-                       complete_p1, row_order_for, skip_p1)
+                       complete_p1, cut_active, cut_order_for, last_shoot_cut, row_order_for, skip_p1)
 
 
 
@@ -337,7 +337,7 @@ class LDDMMModel:
         if sh.p1_missing:
             # what complete_shoot needs to form P[nt] exactly as this shooting would have: the
             # coordinate mode its kernels ran in and the support tensor its row order is keyed on
-            sh.raw, sh.q0_key = raw, q0c
+            sh.raw, sh.q0_key, sh.cut = raw, q0c, last_shoot_cut()
         return sh
 
     def _split(self):
@@ -359,11 +359,17 @@ class LDDMMModel:
                 raw = self._raw_for(key)
             order, order_l = row_order_for(getattr(self, "row_orders", None), key,
                                            float(self.eta), split, shoot.Q.shape[1])
+            # a shooting on the Gaussian-cutoff path (spatial order, boxes): its own last step
+            # (recorded by the shooting itself; a hand-made Shoot without the record: today's rule)
+            cut = getattr(shoot, "cut", None)
+            if cut is None:
+                cut = cut_active(key, False, float(self.eta), self.scheme, split, int(self.nt), raw)
+            cut_order = cut_order_for(getattr(self, "row_orders", None), key) if cut else None
             with _lib.coord_mode(raw):
                 complete_p1(shoot.Q, shoot.P, self.Kernel.sigma, float(self.eta),
                             bool(self.withlogdet), int(self.nt),
                             order=order_l if split is not None else order, split=split,
-                            C=shoot.C)
+                            C=shoot.C, cut_order=cut_order)
             shoot.p1_missing = False
             shoot.q0_key = None
         return shoot

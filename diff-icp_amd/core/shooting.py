@@ -52,6 +52,14 @@ def spatial_order(x: torch.Tensor) -> torch.Tensor:
     return torch.argsort(code, stable=True).to(torch.int32)
 
 
+def inverse_order(order: torch.Tensor) -> torch.Tensor:
+    """The inverse permutation of a row order (int64): x[order][inverse_order(order)] == x."""
+    order = order.long()
+    inv = torch.empty_like(order)
+    inv[order] = torch.arange(order.numel(), device=order.device)
+    return inv
+
+
 class RowOrderCache:
     """spatial_order of the support points, memoised per tensor (q0 is fixed over an L-BFGS
     run: every closure reuses the order).  Keyed on (storage pointer, version counter, shape,
@@ -303,13 +311,15 @@ def last_cost_step(C, Gd, nt, dt):
     torch.add(C[nt - 1], inc[0], out=C[nt])
 
 
-def complete_p1(Q, P, sigma, eta, want_div, nt, order=None, split=None, C=None):
+def complete_p1(Q, P, sigma, eta, want_div, nt, order=None, split=None, C=None, cut_order=None):
     """Form P[nt] of a trajectory shot with need_p1=False: the last Euler step again, by the
     same fused pass a full shooting uses (bitwise the P[nt] it would have produced; row split:
     each rank's slice, one all-gather).  Single device: Q[nt] and (with C) the cost C[nt] are
     rewritten from that pass too -- the mG-less pass of the need_p1=False step may run another
     kernel (the ordered rows where a full pass takes the symmetric 4-row forward, other column
-    splits), so the completed trajectory is bitwise a fresh full shooting's."""
+    splits), so the completed trajectory is bitwise a fresh full shooting's.  cut_order: the
+    spatial order of a shooting that took the cutoff path (cut_active): the step then runs as
+    that shooting's last step does, in that order with the boxes of Q[nt-1]."""
     with torch.no_grad():
         if split is not None:
             M = Q.shape[1]
@@ -334,11 +344,63 @@ def complete_p1(Q, P, sigma, eta, want_div, nt, order=None, split=None, C=None):
         use_zs = bool(want_div) and nt >= 2 and _lib.zs_ok(eta)
         Gd = torch.empty((nt, M), device=Q.device, dtype=Q.dtype) if want_div else None
         zs = torch.empty((M, D), device=Q.device, dtype=Q.dtype) if use_zs else None
+        if cut_order is not None:
+            perm = cut_order.long()
+            inv = inverse_order(perm)
+            qs, ps = Q[nt - 1].index_select(0, perm), P[nt - 1].index_select(0, perm)
+            qn, pn, _ = _lib.euler_step(qs, ps, sigma, eta, 1.0 / nt, want_div,
+                                        g_out=Gd[nt - 1] if want_div else None, zs_out=zs,
+                                        boxes=_lib.pair_boxes(qs, sigma))
+            torch.index_select(qn, 0, inv, out=Q[nt])
+            torch.index_select(pn, 0, inv, out=P[nt])
+            if C is not None and want_div:
+                last_cost_step(C, Gd, nt, 1.0 / nt)
+            return
         _lib.euler_step(Q[nt - 1], P[nt - 1], sigma, eta, 1.0 / nt, want_div, q_out=Q[nt],
                         p_out=P[nt], g_out=Gd[nt - 1] if want_div else None, order=order,
                         zs_out=zs)
         if C is not None and want_div:
             last_cost_step(C, Gd, nt, 1.0 / nt)
+
+
+# ---- Gaussian cutoff of far tile pairs ---------------------------
+# A dense Euler self-shooting at eta = 0 may run in the spatial (Morton) order of q0 with one
+# bounding box per 64 consecutive points of every state: the symmetric kernels then skip the
+# tile pairs whose boxes are farther apart than the cutoff (K < 2^-T, library options
+# pair_cutoff / pair_cutoff_log2).  The order is taken from q0 only (memoised per q0, which is
+# fixed over an L-BFGS run); the boxes are rebuilt per state, so they stay exact as the points
+# move.  Two O(M) gathers per shooting: inputs into the order, outputs back out of it.
+_cut_orders = RowOrderCache()
+# whether the calling thread's latest ShootFn forward took the cutoff path: LDDMMModel.Shoot
+# records it on the Shoot it returns (as raw and q0_key), so a later completion takes that path
+_cut_tl = threading.local()
+
+
+def last_shoot_cut() -> bool:
+    return bool(getattr(_cut_tl, "last", False))
+
+
+def cut_order_for(orders, q0):
+    """The spatial order a cutoff shooting of q0 runs in (int32; memoised per q0)."""
+    return (orders if orders is not None else _cut_orders).get(q0)
+
+
+def cut_active(q0, has_x, eta, scheme, split, nt, raw):
+    """Whether this shooting takes the cutoff path: option pair_cutoff 1 (automatic) from
+    _lib.CUT_MIN_M points, 2 at every size; device tensors, dense Euler self-shooting, eta = 0,
+    the symmetric packed kernels (zs_ok), scaled coordinates, no row split, no frame batching
+    and not the captured-graph path (which pair_cutoff = 2 overrides)."""
+    if not q0.is_cuda or has_x or eta != 0 or scheme != "Euler" or split is not None or raw or nt < 1:
+        return False
+    mode = _lib.get_option("pair_cutoff")
+    if mode == 0 or (mode == 1 and q0.shape[0] < _lib.CUT_MIN_M):
+        return False
+    if (getattr(_lib._tl, "batcher", None) is not None or getattr(_lib._tl, "batch_keep", None) is not None
+            or _lib.get_option("batch_share") != 1):
+        return False
+    if getattr(_graph_tl, "inside", False) or (mode == 1 and _graph_eligible(q0, nt)):
+        return False
+    return _lib.get_option("fwd_alg") in (2, 5, 6) and _lib.get_option("bwd_alg") == 3
 
 
 class ShootFn(torch.autograd.Function):
@@ -381,11 +443,14 @@ class ShootFn(torch.autograd.Function):
         # cotangent's dL/dp term instead of re-summing it pair by pair (saved, nt x M x D floats)
         use_zs = bool(want_div) and scheme == "Euler" and not has_x and nt >= 2 and _lib.zs_ok(eta)
         ctx.has_zs = use_zs
+        cut = cut_active(q0, has_x, eta, scheme, split, nt, ctx.raw)
+        ctx.cut = cut
+        _cut_tl.last = cut
         # option_epoch: a set_option of a kernel variant between two shootings is a miss (the
         # cached trajectory would not be bitwise what the new variant computes)
         params = (float(sigma), float(eta), int(nt), scheme, bool(want_div),
                   None if split is None else (split.rank, split.world, getattr(split, "overlap", False)),
-                  skip, use_zs, ctx.raw,
+                  skip, use_zs, ctx.raw, cut,
                   _lib.option_epoch(), _lib.get_option("batch_share"))
         hit = cache.lookup(q0, p0, x0, params) if cache is not None else None
         if hit is not None:
@@ -401,6 +466,16 @@ class ShootFn(torch.autograd.Function):
         if split is not None and (has_x or scheme != "Euler" or split.world == 1):
             split = None
         ctx.split = split
+        if cut:
+            outs, saved = _cut_forward(q0, p0, sigma, eta, nt, want_div, skip, use_zs, orders)
+            ctx.sigma, ctx.eta, ctx.nt, ctx.scheme, ctx.want_div, ctx.has_x = \
+                sigma, eta, nt, scheme, want_div, has_x
+            ctx.save_for_backward(*saved)
+            if cache is not None:
+                kept = tuple(t.detach() for t in outs)
+                cache.store(q0, p0, x0, params, kept, [t.detach() for t in saved])
+                return _fresh(kept)
+            return outs
         if split is None and not has_x and scheme == "Euler" and _graph_eligible(q0, nt):
             # small supports: the whole fused shooting replayed as one captured HIP graph
             order, _ = row_order_for(orders, q0, eta, None, q0.shape[0])
@@ -655,6 +730,8 @@ class ShootFn(torch.autograd.Function):
             ctx.sigma, ctx.eta, ctx.nt, ctx.scheme, ctx.want_div, ctx.has_x
         split = ctx.split
         saved = ctx.saved_tensors
+        if getattr(ctx, "cut", False):
+            return _cut_backward(ctx, gQ, gP, gC, gH, saved)
         Zs = saved[-1] if ctx.has_zs else None
         if Zs is not None and not _lib.zs_ok(eta):
             Zs = None   # the VJP variant changed since the forward: re-sum the divergence terms
@@ -780,6 +857,89 @@ class ShootFn(torch.autograd.Function):
         if not ctx.needs_input_grad[0]:
             lq = None
         return lq, lp, (lx if has_x else None), None, None, None, None, None, None, None, None, None, None
+
+
+def _cut_forward(q0, p0, sigma, eta, nt, want_div, skip, use_zs, orders):
+    """The fused Euler shooting of ShootFn in the spatial order of q0, every step given the boxes
+    of its state.  Returns (outs in natural row order, saved): saved = [Q, P, v0, mG0, (Zs,) boxes,
+    order, inverse order], the states, divergence rows and boxes in spatial order."""
+    M, D = q0.shape
+    dev = q0.device
+    dt = 1.0 / nt
+    perm = cut_order_for(orders, q0).long()
+    inv = inverse_order(perm)
+    Q = torch.empty((nt + 1, M, D), device=dev, dtype=q0.dtype)
+    P = torch.empty_like(Q)
+    C = torch.zeros((nt + 1, 1), device=dev, dtype=q0.dtype)
+    torch.index_select(q0.detach(), 0, perm, out=Q[0])
+    torch.index_select(p0.detach(), 0, perm, out=P[0])
+    nB = (M + _lib.CUT_TILE - 1) // _lib.CUT_TILE
+    B = torch.empty((nt + 1, nB, 2 * D), device=dev, dtype=q0.dtype)
+    Zs = torch.empty((nt, M, D), device=dev, dtype=q0.dtype) if use_zs else None
+    Gd = torch.empty((nt, M), device=dev, dtype=q0.dtype) if (want_div and nt >= 2) else None
+    Qv, Pv, Bv = Q.unbind(0), P.unbind(0), B.unbind(0)
+    _lib.pair_boxes(Qv[0], sigma, out=Bv[0])
+    v0, mG0, g = _lib.ode_self_fwd_box(Qv[0], Pv[0], sigma, eta, want_div, Bv[0],
+                                       zs_out=None if Zs is None else Zs[0])
+    H0 = _h_rows(Pv[0], v0).sum()
+    torch.add(Qv[0], v0, alpha=dt, out=Qv[1])
+    torch.add(Pv[0], mG0, alpha=dt, out=Pv[1])
+    _lib.pair_boxes(Qv[1], sigma, out=Bv[1])
+    if want_div:
+        torch.add(C[0], g.sum().reshape(1), alpha=dt, out=C[1])
+    for t in range(1, nt):
+        last_skip = skip and t == nt - 1
+        _lib.euler_step(Qv[t], Pv[t], sigma, eta, dt, want_div, q_out=Qv[t + 1], p_out=Pv[t + 1],
+                        g_out=Gd[t] if want_div else None, want_p=not last_skip,
+                        zs_out=None if Zs is None else Zs[t], boxes=Bv[t], boxes_out=Bv[t + 1])
+        if last_skip:
+            Pv[t + 1].fill_(float("nan"))   # not formed: make any read loud
+    if nt >= 2:
+        if want_div:   # the cost of the fused steps, as ShootFn._forward forms it
+            if nt > 2:
+                inc = Gd[1:nt - 1].sum(1, keepdim=True).mul_(dt)
+                torch.cumsum(inc, 0, out=C[2:nt])
+                C[2:nt].add_(C[1])
+            last_cost_step(C, Gd, nt, dt)
+        else:
+            C[2:].copy_(C[1].expand(nt - 1, 1))
+    saved = [Q, P, v0, mG0] + ([Zs] if Zs is not None else []) + [B, perm, inv]
+    return (Q.index_select(1, inv), P.index_select(1, inv), C, H0), saved
+
+
+def _cut_backward(ctx, gQ, gP, gC, gH, saved):
+    """The adjoint of _cut_forward: the cotangents gathered into the spatial order, the fused
+    adjoint steps given the forward's boxes, the gradients scattered back."""
+    sigma, eta, nt, want_div = ctx.sigma, ctx.eta, ctx.nt, ctx.want_div
+    Q, P, v0, mG0 = saved[:4]
+    B, perm, inv = saved[-3:]
+    Zs = saved[4] if ctx.has_zs else None
+    if Zs is not None and not _lib.zs_ok(eta):
+        Zs = None   # the VJP variant changed since the forward: re-sum the divergence terms
+    dt = 1.0 / nt
+    M, D = Q.shape[1], Q.shape[2]
+    dev = Q.device
+    gQ = None if gQ is None else gQ.index_select(1, perm)
+    gP = None if gP is None else gP.index_select(1, perm)
+    lq = gQ[nt].clone() if gQ is not None else torch.zeros((M, D), device=dev, dtype=Q.dtype)
+    lp = gP[nt].clone() if gP is not None else None
+    lc = gC[nt].clone() if gC is not None else torch.zeros((1,), device=dev, dtype=Q.dtype)
+    lcv = None
+    if gC is not None:
+        lcv = torch.flip(torch.cumsum(torch.flip(gC, (0,)), 0), (0,)).unbind(0)
+    Qv, Pv, Bv = Q.unbind(0), P.unbind(0), B.unbind(0)
+    for t in range(nt - 1, -1, -1):
+        lct = lc if gC is None else lcv[t + 1]
+        want_lq = t > 0 or ctx.needs_input_grad[0]
+        lq, lp = _lib.euler_adjoint_step(Qv[t], Pv[t], lq, lp, lct if want_div else None, sigma, eta, dt,
+                                         None if gQ is None else gQ[t], None if gP is None else gP[t],
+                                         want_lq=want_lq, zs=None if Zs is None else Zs[t], boxes=Bv[t])
+    if gH is not None:
+        if lq is not None:
+            lq = lq - gH * mG0
+        lp = lp + gH * v0
+    lq = lq.index_select(0, inv) if (lq is not None and ctx.needs_input_grad[0]) else None
+    return lq, lp.index_select(0, inv), None, None, None, None, None, None, None, None, None, None, None
 
 
 class ManualCtx:
@@ -1047,7 +1207,7 @@ def shoot_loss_grad(LM, dataloss, q0, p0):
     sh = Shoot(Q, P, C, None, H0)
     sh.p1_missing = skip_p1(False, LM.scheme, False, float(LM.eta), None, nt)
     if sh.p1_missing:
-        sh.raw, sh.q0_key = raw, q0.contiguous()
+        sh.raw, sh.q0_key, sh.cut = raw, q0.contiguous(), bool(ctx.cut)
     vg = getattr(dataloss, "value_and_grad", None)
     r = vg(Q[nt]) if (vg is not None and isinstance(LM.lam, (int, float))) else None
     if r is not None:

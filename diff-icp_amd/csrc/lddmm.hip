@@ -255,6 +255,16 @@ extern "C" int dicp_set_option(const char* name, int value) {
     sym_red_rows() = value;
     return DICP_OK;
   }
+  if (!strcmp(name, "pair_cutoff")) {   // Gaussian cutoff of far tile pairs: 0 off, 1 automatic, 2 always
+    if (value < 0 || value > 2) return DICP_ERR_INVALID;
+    pair_cutoff() = value;
+    return DICP_OK;
+  }
+  if (!strcmp(name, "pair_cutoff_log2")) {   // T: a skipped pair has K < 2^-T (kPairCutoffLog2)
+    if (value < 8 || value > 150) return DICP_ERR_INVALID;
+    pair_cutoff_log2() = value;
+    return DICP_OK;
+  }
   if (value != 1 && value != 2 && value != 4) return DICP_ERR_INVALID;
   if (!strcmp(name, "r_fwd")) { g_r_fwd = value; return DICP_OK; }
   if (!strcmp(name, "r_bwd")) { g_r_bwd = value; return DICP_OK; }
@@ -288,6 +298,8 @@ extern "C" int dicp_get_option(const char* name, int* value) {
   if (!strcmp(name, "sym_fwd_rows")) { *value = sym_fwd_rows(); return DICP_OK; }
   if (!strcmp(name, "ext_alg")) { *value = g_ext_alg; return DICP_OK; }
   if (!strcmp(name, "coord_raw")) { *value = tl_coord_raw; return DICP_OK; }
+  if (!strcmp(name, "pair_cutoff")) { *value = pair_cutoff(); return DICP_OK; }
+  if (!strcmp(name, "pair_cutoff_log2")) { *value = pair_cutoff_log2(); return DICP_OK; }
   if (!strcmp(name, "r_fwd")) { *value = r_fwd(); return DICP_OK; }
   if (!strcmp(name, "r_bwd")) { *value = r_bwd(); return DICP_OK; }
   set_error("dicp_get_option: unknown option %s", name);
@@ -996,6 +1008,83 @@ extern "C" int dicp_lddmm_euler_step_zs_f32(const float* q, const float* p, int6
     case 3: return ode_self_fwd_d<3>(q, p, M, sigma, eta, o, ws, ws_bytes, st, row0, nrows, row_order, zs);
     default: set_error("euler_step_ord: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
   }
+}
+
+// ---- the fused steps with the Gaussian cutoff of far tile pairs (lddmm_sym.hpp kCutTile) ----
+// boxes: dicp_pair_boxes_f32 of q (ceil(M / 64) x 2D floats), or NULL = the dense entry above,
+// bit for bit.  With boxes the symmetric 4 / 6 / 8-row forward and the 4-row packed VJP skip far
+// (row group, 64-column sub-tile) pairs; a pass that runs another kernel (the ordered rows below
+// the symmetric forward's size, the mG-less last step, the 2-row VJP) ignores them.  Whole
+// passes, eta = 0, scaled coordinates (not coord_raw), outside launch batches.
+namespace {
+int cut_check(const char* what, const float* boxes, double eta) {
+  if (boxes == nullptr) return DICP_OK;
+  if (eta != 0.0 || tl_coord_raw != 0 || batching()) {
+    set_error("%s: boxes need eta = 0, scaled coordinates and no launch batch", what);
+    return DICP_ERR_INVALID;
+  }
+  return DICP_OK;
+}
+template <int D>
+int pair_boxes_d(const float* q, int64_t M, double sigma, float* boxes, hipStream_t st) {
+  Args a = {nullptr, nullptr, nullptr, nullptr, q, nullptr, nullptr, nullptr, 0.f};
+  Scal sc = make_scal(sigma, 0.0);
+  scale_coords(a, sc, sigma);
+  return launch_pair_boxes<D>(a, M, boxes, st);
+}
+}  // namespace
+
+extern "C" int dicp_pair_boxes_f32(const float* q, int64_t M, int D, double sigma, float* boxes,
+                                   dicp_stream_t stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (M < 0 || (M > 0 && (!q || !boxes)) || !(sigma > 0)) {
+    set_error("dicp_pair_boxes_f32: invalid arguments");
+    return DICP_ERR_INVALID;
+  }
+  switch (D) {
+    case 2: return pair_boxes_d<2>(q, M, sigma, boxes, st);
+    case 3: return pair_boxes_d<3>(q, M, sigma, boxes, st);
+    default: set_error("pair_boxes: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
+  }
+}
+
+extern "C" int dicp_lddmm_ode_self_fwd_box_f32(const float* q, const float* p, int64_t M, int D, double sigma,
+                                               double eta, float* v, float* mG, float* g, float* zs,
+                                               const float* boxes, void* ws, size_t ws_bytes,
+                                               dicp_stream_t stream) {
+  if (int rc = cut_check("dicp_lddmm_ode_self_fwd_box_f32", boxes, eta)) return rc;
+  dicp::CutScope cut_(boxes);
+  if (zs != nullptr)
+    return dicp_lddmm_ode_self_fwd_zs_f32(q, p, M, 0, M, D, sigma, eta, nullptr, v, mG, g, zs, ws, ws_bytes, stream);
+  return dicp_lddmm_ode_self_fwd_ord_f32(q, p, M, 0, M, D, sigma, eta, nullptr, v, mG, g, nullptr, ws, ws_bytes,
+                                         stream);
+}
+
+extern "C" int dicp_lddmm_euler_step_box_f32(const float* q, const float* p, int64_t M, int D, double sigma,
+                                             double eta, double dt, float* q_next, float* p_next, float* g,
+                                             float* zs, const float* boxes, float* boxes_next, void* ws,
+                                             size_t ws_bytes, dicp_stream_t stream) {
+  if (int rc = cut_check("dicp_lddmm_euler_step_box_f32", boxes, eta)) return rc;
+  {
+    dicp::CutScope cut_(boxes);
+    if (int rc = dicp_lddmm_euler_step_zs_f32(q, p, M, 0, M, D, sigma, eta, dt, nullptr, q_next, p_next, g, zs, ws,
+                                              ws_bytes, stream))
+      return rc;
+  }
+  // the new state's boxes, on the same stream after the step's merge wrote q_next
+  return boxes_next != nullptr ? dicp_pair_boxes_f32(q_next, M, D, sigma, boxes_next, stream) : DICP_OK;
+}
+
+extern "C" int dicp_lddmm_euler_adjoint_step_box_f32(const float* q, const float* p, const float* lq,
+                                                     const float* lp, const float* gdiv, int64_t M, int D,
+                                                     double sigma, double eta, double dt, const float* addq,
+                                                     const float* addp, const float* zs, const float* boxes,
+                                                     float* lq_next, float* lp_next, void* ws, size_t ws_bytes,
+                                                     dicp_stream_t stream) {
+  if (int rc = cut_check("dicp_lddmm_euler_adjoint_step_box_f32", boxes, eta)) return rc;
+  dicp::CutScope cut_(boxes);
+  return dicp_lddmm_euler_adjoint_step_zs_f32(q, p, lq, lp, gdiv, M, D, sigma, eta, dt, addq, addp, zs, lq_next,
+                                              lp_next, ws, ws_bytes, stream);
 }
 
 extern "C" int dicp_lddmm_euler_step_ord_f32(const float* q, const float* p, int64_t M,

@@ -50,6 +50,38 @@ inline int& sym_L() {
 }
 // padding coordinate: K = exp2(-|z|^2) = 0 against real points
 constexpr float kFar = 1.0e12f;
+
+// ---- Gaussian cutoff of far tile pairs ----
+// The symmetric 4 / 6 / 8-row kernels may skip the 64-step loop of a (row group, 64-column
+// sub-tile) pair whose bounding boxes are more than sqrt(T) apart in scaled coordinates, where
+// K = 2^(-|z'|^2) < 2^-T for every pair of the two tiles.  Boxes: one per kCutTile consecutive
+// points, lo[D] then hi[D], ceil(M / kCutTile) x 2D floats (pair_boxes_kernel, lddmm_sym_pk.hpp).
+constexpr int kCutTile = 64;
+// T = 48: a skipped pair has K < 2^-48.  The pair terms of the forward and of the VJP are K
+// times a polynomial of degree <= 2 in |z'| with unit-scale coefficients, bounded by
+// (1 + |z'|^2)^2 >= (1 + T)^2 at the cut and decaying beyond it, so the mass a row drops is at
+// most N_far 2^-T (1 + T)^2 relative to unit-scale kept terms: 1e5 far columns give 2^-20.2
+// worst case; measured on the 100k two-set cloud 2^-40 of the kept mass, 2^16 below fp32 epsilon
+// (almost every dropped partial is an exact no-op on the running sum).
+constexpr int kPairCutoffLog2 = 48;
+// dicp_set_option "pair_cutoff": 0 off, 1 automatic (core/shooting.py: dense Euler self-shooting
+// at eta = 0 from 32768 points), 2 on at every size; "pair_cutoff_log2" = T (8 .. 150)
+inline int& pair_cutoff() {
+  static int v = 1;
+  return v;
+}
+inline int& pair_cutoff_log2() {
+  static int v = kPairCutoffLog2;
+  return v;
+}
+// the boxes of the state of the calling thread's current *_box_f32 entry (NULL: dense kernels)
+inline thread_local const float* tl_cut_boxes = nullptr;
+struct CutScope {
+  const float* old;
+  explicit CutScope(const float* b) : old(tl_cut_boxes) { tl_cut_boxes = b; }
+  ~CutScope() { tl_cut_boxes = old; }
+};
+__host__ __device__ inline int cut_tiles(int64_t M) { return (int)((M + kCutTile - 1) / kCutTile); }
 // s_waitcnt lgkmcnt(0) with vmcnt / expcnt left at their maxima (gfx9 encoding)
 constexpr int kLgkm0 = 0xC07F;
 #ifndef DICP_SYM_PREFETCH
@@ -1007,6 +1039,10 @@ __global__ void sym_fwd_pk4_kernel(Args a, Scal sc, int64_t M, int nG, int L, fl
                                    int64_t slot_stride);
 template <int D, bool DIV>
 int sym_fwd_pk4_batch_flush(const std::vector<const void*>& es, hipStream_t st);
+// with the Gaussian cutoff (boxes of the state, T = the cut in scaled squared distance)
+template <int D, bool DIV>
+__global__ void sym_fwd_pk4_cut_kernel(Args a, Scal sc, int64_t M, int nG, int L, float* __restrict__ slab,
+                                       int64_t slot_stride, const float* __restrict__ boxes, float T);
 
 // zs: the divergence rows out through the h slot (o.ptr[3], M x D), DIV required
 template <int D, bool DIV>
@@ -1038,7 +1074,11 @@ int launch_sym_fwd4(const Args& a, const Scal& sc, int64_t M, const Outs& o, voi
             : batch_record(sym_fwd4_merge_batch_flush<D, DIV, false>, e);
     return rc ? rc : check_launch("ode_self_fwd(sym4 merge)");
   }
-  sym_fwd_pk4_kernel<D, DIV><<<grid, dim3(256), 0, st>>>(a, sc, M, g.nG, g.L, slab, stride);
+  if (tl_cut_boxes != nullptr)
+    sym_fwd_pk4_cut_kernel<D, DIV><<<grid, dim3(256), 0, st>>>(a, sc, M, g.nG, g.L, slab, stride, tl_cut_boxes,
+                                                              (float)pair_cutoff_log2());
+  else
+    sym_fwd_pk4_kernel<D, DIV><<<grid, dim3(256), 0, st>>>(a, sc, M, g.nG, g.L, slab, stride);
   int rc = check_launch("ode_self_fwd(sym4)");
   if (rc) return rc;
   if (zs)
@@ -1172,9 +1212,22 @@ int sym_bwd_pk_batch_flush(const std::vector<const void*>& es, hipStream_t st);
 template <int D, bool GQ, bool B0, bool GT, bool RAW>
 int sym_bwd_pk4_batch_flush(const std::vector<const void*>& es, hipStream_t st);
 
+// with the Gaussian cutoff: whole passes in scaled coordinates only (nparts = 1, RAW = false)
+template <int D, bool GQ, bool B0, bool GT>
+__global__ void sym_bwd_pk4_cut_kernel(Args a, Scal sc, int64_t M, int nG, int L, float* __restrict__ slab,
+                                       int64_t slot_stride, const float* __restrict__ boxes, float T);
+
 template <int D, bool GQ, bool B0>
 inline void sym_bwd_pk4_launch(bool gt, bool raw, dim3 grid, hipStream_t st, const Args& a, const Scal& sc,
                                int64_t M, const SymGeom& g, float* slab, int64_t stride, int part, int nparts) {
+  if (tl_cut_boxes != nullptr && !batching() && !raw && nparts == 1) {
+    const float T = (float)pair_cutoff_log2();
+    if (gt)
+      sym_bwd_pk4_cut_kernel<D, GQ, B0, true><<<grid, dim3(256), 0, st>>>(a, sc, M, g.nG, g.L, slab, stride, tl_cut_boxes, T);
+    else
+      sym_bwd_pk4_cut_kernel<D, GQ, B0, false><<<grid, dim3(256), 0, st>>>(a, sc, M, g.nG, g.L, slab, stride, tl_cut_boxes, T);
+    return;
+  }
   if (batching()) {
     const SymEntry e{a, sc, M, g.nG, g.L, slab, stride, part, nparts, grid.x, grid.y};
     if (gt && raw) batch_record(sym_bwd_pk4_batch_flush<D, GQ, B0, true, true>, e);

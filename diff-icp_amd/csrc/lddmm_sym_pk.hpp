@@ -10,6 +10,117 @@
 
 namespace dicp {
 
+// ---- Gaussian cutoff of far tile pairs (lddmm_sym.hpp kCutTile) ----
+template <int D>
+struct CutBox {
+  float lo[D], hi[D];
+};
+// a wave-uniform float, held in a scalar register from here on
+__device__ __forceinline__ float cut_uniform(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
+}
+// min / max that keep a NaN of either operand (fminf / fmaxf would drop it)
+__device__ __forceinline__ float nan_min(float a, float b) { return (b < a || b != b) ? b : a; }
+__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
+template <int D>
+__device__ __forceinline__ void cut_load(const float* __restrict__ boxes, int s, CutBox<D>& b) {
+#pragma unroll
+  for (int d = 0; d < D; ++d) {
+    b.lo[d] = boxes[(int64_t)s * (2 * D) + d];
+    b.hi[d] = boxes[(int64_t)s * (2 * D) + D + d];
+  }
+}
+// box of the N sub-tiles from s0 on (those below nB): the row group of a wave; s0 wave-uniform
+template <int D, int N>
+__device__ __forceinline__ void cut_row_box(const float* __restrict__ boxes, int s0, int nB, CutBox<D>& r) {
+#pragma unroll
+  for (int d = 0; d < D; ++d) r.lo[d] = __builtin_huge_valf(), r.hi[d] = -__builtin_huge_valf();
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    if (s0 + k >= nB) break;
+    CutBox<D> b;
+    cut_load<D>(boxes, s0 + k, b);
+#pragma unroll
+    for (int d = 0; d < D; ++d) r.lo[d] = nan_min(r.lo[d], b.lo[d]), r.hi[d] = nan_max(r.hi[d], b.hi[d]);
+  }
+#pragma unroll
+  for (int d = 0; d < D; ++d) r.lo[d] = cut_uniform(r.lo[d]), r.hi[d] = cut_uniform(r.hi[d]);
+}
+// bit h set: sub-tile h of column group B (N sub-tiles) is farther than sqrt(T) from the row box,
+// i.e. sum_d max(0, lo_r - hi_c, lo_c - hi_r)^2 > T; a NaN box (a non-finite coordinate) gives
+// gap2 = 0 or NaN and is never far
+template <int D, int N>
+__device__ __forceinline__ unsigned cut_mask(const float* __restrict__ boxes, const CutBox<D>& r, int B, int nB,
+                                             float T) {
+  unsigned m = 0;
+#pragma unroll
+  for (int h = 0; h < N; ++h) {
+    const int s = B * N + h;
+    if (s >= nB) break;
+    CutBox<D> c;
+    cut_load<D>(boxes, s, c);
+    float gap2 = 0.f;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      const float a = r.lo[d] - c.hi[d], b = c.lo[d] - r.hi[d];
+      float g = a > b ? a : b;
+      g = g > 0.f ? g : 0.f;
+      gap2 = fmaf(g, g, gap2);
+    }
+    if (gap2 > T) m |= 1u << h;
+  }
+  return (unsigned)__builtin_amdgcn_readfirstlane((int)m);
+}
+
+// One box per kCutTile consecutive points of q in the kernels' scaled coordinates
+// alpha (q - shift) (ld_coord): one wave per sub-tile, lo / hi by a wave min / max; a sub-tile
+// with a non-finite coordinate gets an all-NaN box.
+template <int D>
+__global__ __launch_bounds__(256) void pair_boxes_kernel(Args a, int64_t M, int nB, float* __restrict__ boxes) {
+  const int s = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), l = threadIdx.x & 63;
+  if (s >= nB) return;
+  const int64_t i = (int64_t)s * kCutTile + l;
+  float lo[D], hi[D];
+  bool bad = false;
+  if (i < M) {
+    float c[D];
+    ld_coord<D>(a, a.c0, i, c);
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      lo[d] = hi[d] = c[d];
+      bad = bad || !(fabsf(c[d]) < __builtin_huge_valf());
+    }
+  } else {
+#pragma unroll
+    for (int d = 0; d < D; ++d) lo[d] = __builtin_huge_valf(), hi[d] = -__builtin_huge_valf();
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      lo[d] = fminf(lo[d], __shfl_xor(lo[d], off, 64));
+      hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], off, 64));
+    }
+  }
+  const bool anybad = __any(bad);
+  if (l < 2 * D) {
+    float v = 0.f;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      if (l == d) v = lo[d];
+      if (l == D + d) v = hi[d];
+    }
+    boxes[(int64_t)s * (2 * D) + l] = anybad ? __builtin_nanf("") : v;
+  }
+}
+template <int D>
+int launch_pair_boxes(const Args& a, int64_t M, float* boxes, hipStream_t st) {   // a: c0 = q, scale, shift
+  if (M <= 0) return DICP_OK;
+  const int nB = cut_tiles(M);
+  pair_boxes_kernel<D><<<dim3((unsigned)((nB + 3) / 4)), dim3(256), 0, st>>>(a, M, nB, boxes);
+  return check_launch("pair_boxes");
+}
+
 // GQ = false: the gp half only (dL/dp of the VJP), for the last adjoint step of a shooting
 // whose start points need no gradient (the support points in Reg_opt): the pair scalars
 // pp, u, zu, iap, w and every gq accumulation drop out -- 32 of the 60 packed instructions
@@ -476,10 +587,14 @@ __device__ __forceinline__ void sym_pk_body(Args a, Scal sc, int64_t M, int nG, 
 #ifndef DICP_SYMBWD4_WMIN
 #define DICP_SYMBWD4_WMIN 1
 #endif
-template <class P>
+// DC > 0 (= D): with the Gaussian cutoff -- a wave skips the 64-step loop of a sub-tile whose box is
+// far from its row group's (cut_mask); its zero column sums and every barrier stay.  DC = 0 is
+// the dense body, unchanged.
+template <class P, int DC = 0>
 __device__ __forceinline__ void sym_pk4_body(Args a, Scal sc, int64_t M, int nG, int L,
                                              float* __restrict__ slab, int64_t slot_stride, int qoff,
-                                             int qstride, unsigned bx, unsigned by) {
+                                             int qstride, unsigned bx, unsigned by,
+                                             const float* __restrict__ boxes = nullptr, float T = 0.f) {
   using S = typename P::S;
   using LY = rec_layout<P>;
   constexpr int G = kSymG4;
@@ -515,6 +630,10 @@ __device__ __forceinline__ void sym_pk4_body(Args a, Scal sc, int64_t M, int nG,
   for (int h = 0; h < 2; ++h)
 #pragma unroll
     for (int k = 0; k < W; ++k) racc[h][k] = splat(0.f);
+
+  CutBox<(DC > 0 ? DC : 1)> rbox;
+  const int nB = cut_tiles(M);
+  if constexpr (DC > 0) cut_row_box<DC, G / 64>(boxes, __builtin_amdgcn_readfirstlane(A) * (G / 64), nB, rbox);
 
   auto stage = [&](int B, int buf) {
     const int64_t j = (int64_t)B * G + tid;   // 256 threads: one record each
@@ -564,12 +683,16 @@ __device__ __forceinline__ void sym_pk4_body(Args a, Scal sc, int64_t M, int nG,
     if (B + 1 < B1) stage(B + 1, buf ^ 1);
     const bool sym = A < B;          // wave-uniform
     const bool diag = A == B;
+    unsigned far = 0;
+    if constexpr (DC > 0) {
+      if (sym) far = cut_mask<DC, G / 64>(boxes, rbox, B, nB, T);
+    }
 #pragma unroll 1
     for (int h = 0; h < G / 64; ++h) {
       float cacc[W];
 #pragma unroll
       for (int k = 0; k < W; ++k) cacc[k] = 0.f;
-      if (sym) {
+      if (sym && !((far >> h) & 1u)) {
 #pragma unroll DICP_SYMBWD4_UNROLL
         for (int k2 = 0; k2 < 64; ++k2) {
           const int col = h * 64 + ((l + k2) & 63);
@@ -632,6 +755,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DICP_SYMBWD
     int qstride) {
   sym_pk_body<SymBwdPk<D, GQ, B0, GT, RAW>>(a, sc, M, nG, L, slab, slot_stride, qoff, qstride, blockIdx.x,
                                             blockIdx.y);
+}
+
+template <int D, bool GQ, bool B0, bool GT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DICP_SYMBWD4_WMIN, 4))) void sym_bwd_pk4_cut_kernel(
+    Args a, Scal sc, int64_t M, int nG, int L, float* __restrict__ slab, int64_t slot_stride,
+    const float* __restrict__ boxes, float T) {
+  sym_pk4_body<SymBwdPk<D, GQ, B0, GT, false>, D>(a, sc, M, nG, L, slab, slot_stride, 0, 1, blockIdx.x, blockIdx.y,
+                                                  boxes, T);
 }
 
 // batched forms (batch.hpp): blockIdx.z = the recorded call (SymEntry, lddmm_sym.hpp)
@@ -1022,10 +1153,11 @@ struct SymFwdPkN {
 #ifndef DICP_SYMFWD8_WPE
 #define DICP_SYMFWD8_WPE 1
 #endif
-template <int D, bool DIV, int NRP>
+template <int D, bool DIV, int NRP, bool CUT = false>
 __device__ __forceinline__ void sym_fwd_pkn_body(const Args& a, const Scal& sc, int64_t M, int nG, int L,
                                                  float* __restrict__ slab, int64_t slot_stride, unsigned bx,
-                                                 unsigned by) {
+                                                 unsigned by, const float* __restrict__ boxes = nullptr,
+                                                 float T = 0.f) {
   using P = SymFwdPkN<D, DIV, NRP>;
   using P4 = SymFwdPk4<D, DIV>;
   using S = typename P::S;
@@ -1062,6 +1194,10 @@ __device__ __forceinline__ void sym_fwd_pkn_body(const Args& a, const Scal& sc, 
   for (int h = 0; h < NRP; ++h)
 #pragma unroll
     for (int k = 0; k < W; ++k) racc[h][k] = splat(0.f);
+
+  CutBox<D> rbox;
+  const int nB = cut_tiles(M);
+  if constexpr (CUT) cut_row_box<D, G / 64>(boxes, __builtin_amdgcn_readfirstlane(A) * (G / 64), nB, rbox);
 
   auto stage = [&](int B, int buf) {
 #pragma unroll
@@ -1103,13 +1239,17 @@ __device__ __forceinline__ void sym_fwd_pkn_body(const Args& a, const Scal& sc, 
     if (B + 1 < B1) stage(B + 1, buf ^ 1);
     const bool sym = A < B;          // wave-uniform
     const bool diag = A == B;
+    unsigned far = 0;
+    if constexpr (CUT) {
+      if (sym) far = cut_mask<D, G / 64>(boxes, rbox, B, nB, T);
+    }
 #pragma unroll 1
     for (int h = 0; h < G / 64; ++h) {   // 64-column slices of the group
       {
         float cacc[W];
 #pragma unroll
         for (int k = 0; k < W; ++k) cacc[k] = 0.f;
-        if (sym) {
+        if (sym && !((far >> h) & 1u)) {
 #pragma unroll 1
           for (int k2 = 0; k2 < 64; ++k2) {
             const int col = h * 64 + ((l + k2) & 63);
@@ -1165,6 +1305,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NRP == 4 ? 
     Args a, Scal sc, int64_t M, int nG, int L, float* __restrict__ slab, int64_t slot_stride) {
   sym_fwd_pkn_body<D, DIV, NRP>(a, sc, M, nG, L, slab, slot_stride, blockIdx.x, blockIdx.y);
 }
+template <int D, bool DIV, int NRP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NRP == 4 ? DICP_SYMFWD8_WPE : 3, 4))) void sym_fwd_pkn_cut_kernel(
+    Args a, Scal sc, int64_t M, int nG, int L, float* __restrict__ slab, int64_t slot_stride,
+    const float* __restrict__ boxes, float T) {
+  sym_fwd_pkn_body<D, DIV, NRP, true>(a, sc, M, nG, L, slab, slot_stride, blockIdx.x, blockIdx.y, boxes, T);
+}
 // one grid over the frames of a lockstep launch batch (batch.hpp), as sym_fwd_pk4_batch_kernel
 template <int D, bool DIV, int NRP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NRP == 4 ? DICP_SYMFWD8_WPE : 3, 4))) void sym_fwd_pkn_batch_kernel(
@@ -1210,7 +1356,11 @@ int launch_sym_fwdn(const Args& a, const Scal& sc, int64_t M, const Outs& o, voi
             : batch_record(sym_fwd4_merge_batch_flush<D, DIV, false, G>, e);
     return rc ? rc : check_launch("ode_self_fwd(sym6/8 merge)");
   }
-  sym_fwd_pkn_kernel<D, DIV, NRP><<<grid, dim3(256), 0, st>>>(a, sc, M, g.nG, g.L, slab, stride);
+  if (tl_cut_boxes != nullptr)
+    sym_fwd_pkn_cut_kernel<D, DIV, NRP><<<grid, dim3(256), 0, st>>>(a, sc, M, g.nG, g.L, slab, stride, tl_cut_boxes,
+                                                                   (float)pair_cutoff_log2());
+  else
+    sym_fwd_pkn_kernel<D, DIV, NRP><<<grid, dim3(256), 0, st>>>(a, sc, M, g.nG, g.L, slab, stride);
   int rc = check_launch("ode_self_fwd(sym6/8)");
   if (rc) return rc;
   if (zs)
@@ -1234,6 +1384,12 @@ template <int D, bool DIV>
 __global__ __launch_bounds__(256) void sym_fwd_pk4_kernel(Args a, Scal sc, int64_t M, int nG, int L,
                                                           float* __restrict__ slab, int64_t slot_stride) {
   sym_pk4_body<SymFwdPk4<D, DIV>>(a, sc, M, nG, L, slab, slot_stride, 0, 1, blockIdx.x, blockIdx.y);
+}
+template <int D, bool DIV>
+__global__ __launch_bounds__(256) void sym_fwd_pk4_cut_kernel(Args a, Scal sc, int64_t M, int nG, int L,
+                                                              float* __restrict__ slab, int64_t slot_stride,
+                                                              const float* __restrict__ boxes, float T) {
+  sym_pk4_body<SymFwdPk4<D, DIV>, D>(a, sc, M, nG, L, slab, slot_stride, 0, 1, blockIdx.x, blockIdx.y, boxes, T);
 }
 template <int D, bool DIV>
 __global__ __launch_bounds__(256) void sym_fwd_pk4_batch_kernel(BatchTab<SymEntry> t) {

@@ -259,6 +259,35 @@ int dicp_lddmm_euler_adjoint_step_zs_f32(const float* q, const float* p, const f
                                          float* lp_next, void* ws, size_t ws_bytes,
                                          dicp_stream_t stream);
 
+/* Gaussian cutoff of far tile pairs (options "pair_cutoff", "pair_cutoff_log2").
+ * dicp_pair_boxes_f32: one bounding box per 64 consecutive points of q (M, D) in the kernels'
+ * scaled coordinates alpha (q - q_0), alpha = sqrt(log2(e) / (2 sigma^2)): boxes is
+ * ceil(M / 64) x 2D floats, lo[D] then hi[D]; a sub-tile with a non-finite coordinate gets NaN.
+ * The *_box_f32 forms below are the whole-pass (row0 = 0, nrows = M, no row order) forms of
+ * dicp_lddmm_ode_self_fwd_zs_f32 (zs may be NULL), dicp_lddmm_euler_step_zs_f32 and
+ * dicp_lddmm_euler_adjoint_step_zs_f32 given the boxes of q: the symmetric 4 / 6 / 8-row forward
+ * and the 4-row packed VJP then skip every (row group, 64-column sub-tile) pair whose boxes are
+ * more than sqrt(T) apart, where K < 2^-T (T = "pair_cutoff_log2"); passes that run another
+ * kernel ignore the boxes.  boxes = NULL is the dense form, bit for bit.  With boxes: eta = 0,
+ * scaled coordinates, no launch batch.  boxes_next (or NULL): the boxes of q_next, formed after
+ * the step. */
+int dicp_pair_boxes_f32(const float* q, int64_t M, int D, double sigma, float* boxes,
+                        dicp_stream_t stream);
+int dicp_lddmm_ode_self_fwd_box_f32(const float* q, const float* p, int64_t M, int D, double sigma,
+                                    double eta, float* v, float* mG, float* g, float* zs,
+                                    const float* boxes, void* ws, size_t ws_bytes,
+                                    dicp_stream_t stream);
+int dicp_lddmm_euler_step_box_f32(const float* q, const float* p, int64_t M, int D, double sigma,
+                                  double eta, double dt, float* q_next, float* p_next, float* g,
+                                  float* zs, const float* boxes, float* boxes_next, void* ws,
+                                  size_t ws_bytes, dicp_stream_t stream);
+int dicp_lddmm_euler_adjoint_step_box_f32(const float* q, const float* p, const float* lq,
+                                          const float* lp, const float* gdiv, int64_t M, int D,
+                                          double sigma, double eta, double dt, const float* addq,
+                                          const float* addp, const float* zs, const float* boxes,
+                                          float* lq_next, float* lp_next, void* ws,
+                                          size_t ws_bytes, dicp_stream_t stream);
+
 /* dicp_lddmm_ode_self_bwd_part_f32 given the zs rows [zrow0, zrow0 + znrows) (a rank's forward
  * slice; NULL = the plain form): part `part` adds their -gdiv zs_i / sigma^2 term, so every
  * row's term is added once over the parts when the ranks' slices tile 0..M-1. */
@@ -410,6 +439,11 @@ int dicp_supports_dim(int D);
  *   "sym_red_rows" rows per lane of the pair-once sums: 0 automatic (4), 4 or 8 forced
  *   "sym_fwd_rows" rows per lane of the symmetric eta = 0 forward: 0 automatic (6 from 40k, 8 from 180k
  *                  points alone on the chip, else 4), 4, 6 or 8 forced
+ *   "pair_cutoff"  Gaussian cutoff of far tile pairs in the symmetric shooting kernels: 0 off, 1
+ *                  automatic (default: dense Euler self-shootings at eta = 0 from 32768 points run in
+ *                  spatial order with boxes), 2 at every size
+ *   "pair_cutoff_log2"  T of the cutoff: tile pairs whose every K is below 2^-T are skipped
+ *                  (default 48, 8 .. 150)
  *   "lse_pk"       GMM E / M passes: 1 rows packed in float2 pairs (v_pk_fma_f32, default),
  *                  0 scalar rows (bitwise equal)
  *   "lse_adapt"    GMM E / M passes: tiles with a tile-end re-reference (anywhere in the
