@@ -72,6 +72,62 @@ __device__ __forceinline__ unsigned cut_mask(const float* __restrict__ boxes, co
   return (unsigned)__builtin_amdgcn_readfirstlane((int)m);
 }
 
+// DICP_CUT_ROWPAIR = 1: the cutoff acts per row pair -- the lane's rows 2k*64 + l and
+// (2k+1)*64 + l, 128 consecutive points, two tile boxes -- instead of per wave: a sub-tile whose
+// box is far from some but not all of a wave's row pairs runs a loop body instantiated for the
+// active ones (pair_sym / pair_sym4 <ACT>).  Every row-pair box lies inside the wave's group box
+// and the predicate is monotone in the box (also in float32), so every sub-tile the wave-level
+// test skips is skipped here too.  0: the wave-level test only.
+#ifndef DICP_CUT_ROWPAIR
+#define DICP_CUT_ROWPAIR 1
+#endif
+constexpr bool kCutRowPair = DICP_CUT_ROWPAIR != 0;
+// boxes of the NRP row pairs of the group whose first sub-tile is s0 (wave-uniform); a row pair
+// past the end of the cloud keeps the empty box (lo = +inf, hi = -inf), which is far from
+// everything: its padding rows contribute K = 0
+template <int D, int NRP>
+__device__ __forceinline__ void cut_rowpair_boxes(const float* __restrict__ boxes, int s0, int nB, CutBox<D>* r) {
+#pragma unroll
+  for (int k = 0; k < NRP; ++k) cut_row_box<D, 2>(boxes, s0 + 2 * k, nB, r[k]);
+}
+// bit h * NRP + k set: sub-tile h of column group B (N sub-tiles) is far from row pair k --
+// cut_mask's predicate and arithmetic against each row-pair box
+template <int D, int N, int NRP>
+__device__ __forceinline__ unsigned cut_mask_rowpair(const float* __restrict__ boxes, const CutBox<D>* r, int B,
+                                                     int nB, float T) {
+  static_assert(N * NRP <= 32, "one mask word");
+  unsigned m = 0;
+#pragma unroll
+  for (int h = 0; h < N; ++h) {
+    const int s = B * N + h;
+    if (s >= nB) break;
+    CutBox<D> c;
+    cut_load<D>(boxes, s, c);
+#pragma unroll
+    for (int k = 0; k < NRP; ++k) {
+      float gap2 = 0.f;
+#pragma unroll
+      for (int d = 0; d < D; ++d) {
+        const float a = r[k].lo[d] - c.hi[d], b = c.lo[d] - r[k].hi[d];
+        float g = a > b ? a : b;
+        g = g > 0.f ? g : 0.f;
+        gap2 = fmaf(g, g, gap2);
+      }
+      if (gap2 > T) m |= 1u << (h * NRP + k);
+    }
+  }
+  return (unsigned)__builtin_amdgcn_readfirstlane((int)m);
+}
+// the loop body of the wave-uniform mask act of active row pairs (0 < act < 2^NRP), all active
+// first: f(std::integral_constant<unsigned, ACT>)
+template <unsigned ACT, class F>
+__device__ __forceinline__ void cut_dispatch(unsigned act, F&& f) {
+  if (act == ACT)
+    f(std::integral_constant<unsigned, ACT>{});
+  else if constexpr (ACT > 1u)
+    cut_dispatch<ACT - 1u>(act, f);
+}
+
 // One box per kCutTile consecutive points of q in the kernels' scaled coordinates
 // alpha (q - shift) (ld_coord): one wave per sub-tile, lo / hi by a wave min / max; a sub-tile
 // with a non-finite coordinate gets an all-NaN box.
@@ -334,8 +390,51 @@ struct SymBwdPk {
   // two row pairs' terms are chained into one float2 and only its two halves are added as
   // scalars -- instead of two scalar FMAs per row and accumulator (4 rows: per D-component
   // 4-5 v_pk + 1 scalar add instead of 8-10 scalar FMAs + 2 adds).
+  // ACT (Gaussian cutoff per row pair, DICP_CUT_ROWPAIR): bit k set = row pair k is active.  A
+  // partial body (ACT = 1, 2) computes what the full one computes with the far row pair's K and
+  // cKzb equal to zero: its shared terms, its row accumulations and its links of the column
+  // chain drop out, the surviving links keep their order and packed form.  The link that now
+  // opens the chain is an FMA onto zero, so that its product is rounded as in the full chain
+  // before the two halves are added.
+  template <unsigned ACT = 3u>
   __device__ static void pair_sym4(const Prm& prm, const Row2& r0, const Row2& r1, const float* rec,
                                    f2* acc0, f2* acc1, float* ct) {
+    static_assert(ACT >= 1u && ACT <= 3u, "mask of active row pairs");
+    if constexpr (ACT != 3u) {
+      constexpr bool kFirst = ACT == 1u;
+      const Row2& r = kFirst ? r0 : r1;
+      f2* acc = kFirst ? acc0 : acc1;
+      const float gt = prm.gt;
+      f2 cv[5 * D];
+      colvec(rec, cv);
+      Shared t;
+      shared_terms(prm, r, cv, t);
+      const f2* pj = cv + D;
+      const f2* aj = cv + 2 * D;
+#pragma unroll
+      for (int d = 0; d < D; ++d) {
+        const f2 ka = GT ? pk_fma(splat(-gt), t.z[d], aj[d]) : aj[d];
+        const f2 tt = GT ? pk_fma(splat(gt), t.z[d], r.ia_a[d]) : r.ia_a[d];
+        f2 cg = pk_fma(t.K, tt, splat(0.f));
+        if constexpr (B0) {
+          acc[d] = pk_fma(t.K, ka, acc[d]);
+        } else {
+          acc[d] = pk_fma(t.cKzb, pj[d], pk_fma(t.K, ka, acc[d]));
+          cg = pk_fma(t.cKzb, r.p[d], cg);
+        }
+        ct[d] = cg.x + cg.y;
+        if constexpr (GQ) {
+          const f2 e = pk_fma(t.w, t.z[d], -t.u[d]);
+          if constexpr (kFirst)
+            acc[D + d] = acc[D + d] + t.K * e;
+          else
+            acc[D + d] = pk_fma(t.K, e, acc[D + d]);
+          const f2 cs = pk_fma(t.K, e, splat(0.f));
+          ct[D + d] = -(cs.x + cs.y);
+        }
+      }
+      return;
+    }
     const float gt = prm.gt;
     f2 cv[5 * D];
     colvec(rec, cv);
@@ -588,8 +687,9 @@ __device__ __forceinline__ void sym_pk_body(Args a, Scal sc, int64_t M, int nG, 
 #define DICP_SYMBWD4_WMIN 1
 #endif
 // DC > 0 (= D): with the Gaussian cutoff -- a wave skips the 64-step loop of a sub-tile whose box is
-// far from its row group's (cut_mask); its zero column sums and every barrier stay.  DC = 0 is
-// the dense body, unchanged.
+// far from its row group's (cut_mask) or, with DICP_CUT_ROWPAIR, from both of its row pairs'
+// (cut_mask_rowpair; far from one: the loop body of the other, pair_sym4<ACT>); its zero column
+// sums and every barrier stay.  DC = 0 is the dense body, unchanged.
 template <class P, int DC = 0>
 __device__ __forceinline__ void sym_pk4_body(Args a, Scal sc, int64_t M, int nG, int L,
                                              float* __restrict__ slab, int64_t slot_stride, int qoff,
@@ -631,9 +731,13 @@ __device__ __forceinline__ void sym_pk4_body(Args a, Scal sc, int64_t M, int nG,
 #pragma unroll
     for (int k = 0; k < W; ++k) racc[h][k] = splat(0.f);
 
-  CutBox<(DC > 0 ? DC : 1)> rbox;
+  constexpr bool kRowPair = DC > 0 && kCutRowPair;
+  CutBox<(DC > 0 ? DC : 1)> rbox, rpbox[2];
   const int nB = cut_tiles(M);
-  if constexpr (DC > 0) cut_row_box<DC, G / 64>(boxes, __builtin_amdgcn_readfirstlane(A) * (G / 64), nB, rbox);
+  if constexpr (kRowPair)
+    cut_rowpair_boxes<DC, 2>(boxes, __builtin_amdgcn_readfirstlane(A) * (G / 64), nB, rpbox);
+  else if constexpr (DC > 0)
+    cut_row_box<DC, G / 64>(boxes, __builtin_amdgcn_readfirstlane(A) * (G / 64), nB, rbox);
 
   auto stage = [&](int B, int buf) {
     const int64_t j = (int64_t)B * G + tid;   // 256 threads: one record each
@@ -685,23 +789,47 @@ __device__ __forceinline__ void sym_pk4_body(Args a, Scal sc, int64_t M, int nG,
     const bool diag = A == B;
     unsigned far = 0;
     if constexpr (DC > 0) {
-      if (sym) far = cut_mask<DC, G / 64>(boxes, rbox, B, nB, T);
+      if (sym) {
+        if constexpr (kRowPair)
+          far = cut_mask_rowpair<DC, G / 64, 2>(boxes, rpbox, B, nB, T);
+        else
+          far = cut_mask<DC, G / 64>(boxes, rbox, B, nB, T);
+      }
     }
 #pragma unroll 1
     for (int h = 0; h < G / 64; ++h) {
       float cacc[W];
 #pragma unroll
       for (int k = 0; k < W; ++k) cacc[k] = 0.f;
-      if (sym && !((far >> h) & 1u)) {
+      // DICP_CUT_ROWPAIR: the wave's active row pairs against sub-tile h (wave-uniform) choose
+      // the loop body; otherwise the one loop, kept as it was
+      unsigned act = 3u;
+      if constexpr (kRowPair) act = ~(far >> (2 * h)) & 3u;
+      if (sym && (kRowPair ? act != 0u : !((far >> h) & 1u))) {
+        if constexpr (kRowPair) {
+          cut_dispatch<3u>(act, [&](auto ac) {
 #pragma unroll DICP_SYMBWD4_UNROLL
-        for (int k2 = 0; k2 < 64; ++k2) {
-          const int col = h * 64 + ((l + k2) & 63);
-          float rec[4 * CW + NP];
-          ldrec(col, rec);
-          float ct[W];
-          P::pair_sym4(prm, row[0], row[1], rec, racc[0], racc[1], ct);
+            for (int k2 = 0; k2 < 64; ++k2) {
+              const int col = h * 64 + ((l + k2) & 63);
+              float rec[4 * CW + NP];
+              ldrec(col, rec);
+              float ct[W];
+              P::template pair_sym4<decltype(ac)::value>(prm, row[0], row[1], rec, racc[0], racc[1], ct);
 #pragma unroll
-          for (int k = 0; k < W; ++k) cacc[k] = rol1(cacc[k]) + ct[k];
+              for (int k = 0; k < W; ++k) cacc[k] = rol1(cacc[k]) + ct[k];
+            }
+          });
+        } else {
+#pragma unroll DICP_SYMBWD4_UNROLL
+          for (int k2 = 0; k2 < 64; ++k2) {
+            const int col = h * 64 + ((l + k2) & 63);
+            float rec[4 * CW + NP];
+            ldrec(col, rec);
+            float ct[W];
+            P::pair_sym4(prm, row[0], row[1], rec, racc[0], racc[1], ct);
+#pragma unroll
+            for (int k = 0; k < W; ++k) cacc[k] = rol1(cacc[k]) + ct[k];
+          }
         }
 #pragma unroll
         for (int k = 0; k < W; ++k) cacc[k] = rol1(cacc[k]);
@@ -1075,8 +1203,32 @@ struct SymFwdPk4 {
     shared(r, cv, t);
     row_side(t, cv, acc);
   }
+  // ACT: the active row pairs (SymBwdPk::pair_sym4); a partial body is the full one with the
+  // far row pair's K = 0
+  template <unsigned ACT = 3u>
   __device__ static void pair_sym4(const Prm&, const Row2& r0, const Row2& r1, const float* rec, f2* acc0,
                                    f2* acc1, float* ct) {
+    static_assert(ACT >= 1u && ACT <= 3u, "mask of active row pairs");
+    if constexpr (ACT != 3u) {
+      const Row2& r = ACT == 1u ? r0 : r1;
+      f2 cv[2 * D];
+      colvec(rec, cv);
+      Sh t;
+      shared(r, cv, t);
+      row_side(t, cv, ACT == 1u ? acc0 : acc1);
+#pragma unroll
+      for (int d = 0; d < D; ++d) {
+        const f2 cV = pk_fma(t.K, r.p[d], splat(0.f));
+        ct[d] = cV.x + cV.y;
+        const f2 cG = pk_fma(t.Kpp, t.z[d], splat(0.f));
+        ct[D + d] = -(cG.x + cG.y);
+        if (DIV) {
+          const f2 cZ = pk_fma(t.K, t.z[d], splat(0.f));
+          ct[2 * D + d] = -(cZ.x + cZ.y);
+        }
+      }
+      return;
+    }
     f2 cv[2 * D];
     colvec(rec, cv);
     Sh t0, t1;
@@ -1119,23 +1271,35 @@ struct SymFwdPkN {
   static constexpr int W = S::W;
   using Row2 = typename P4::Row2;
   using Sh = typename P4::Sh;
+  static constexpr unsigned kAll = (1u << NRP) - 1u;
+  // ACT (Gaussian cutoff per row pair, DICP_CUT_ROWPAIR): bit h set = row pair h is active.  A
+  // partial body computes what the full one computes with the far row pairs' K = 0: their shared
+  // terms, row sides and links of the column chains drop out, the surviving links keep their
+  // order; the chains then open with an FMA onto zero (the product rounded as in the full chain).
+  template <unsigned ACT = kAll>
   __device__ static void pair_sym(const Row2* r, const float* rec, f2 (*acc)[W], float* ct) {
+    static_assert(ACT >= 1u && ACT <= kAll, "mask of active row pairs");
     f2 cv[2 * D];
     P4::colvec(rec, cv);
     // per row pair: its shared terms, row side, and its share of the column side chained into
     // the column partials in row-pair order
     f2 cV[D], cG[D], cZ[D];
+    if constexpr (ACT != kAll) {
+#pragma unroll
+      for (int d = 0; d < D; ++d) cV[d] = cG[d] = cZ[d] = splat(0.f);
+    }
 #pragma unroll
     for (int h = 0; h < NRP; ++h) {
+      if (!((ACT >> h) & 1u)) continue;
       Sh t;
       P4::shared(r[h], cv, t);
       P4::row_side(t, cv, acc[h]);
 #pragma unroll
       for (int d = 0; d < D; ++d) {
         // column j's side over the 2 NRP rows; (i, j) -> (j, i) flips z
-        cV[d] = h == 0 ? t.K * r[h].p[d] : pk_fma(t.K, r[h].p[d], cV[d]);
-        cG[d] = h == 0 ? t.Kpp * t.z[d] : pk_fma(t.Kpp, t.z[d], cG[d]);
-        if (DIV) cZ[d] = h == 0 ? t.K * t.z[d] : pk_fma(t.K, t.z[d], cZ[d]);
+        cV[d] = (ACT == kAll && h == 0) ? t.K * r[h].p[d] : pk_fma(t.K, r[h].p[d], cV[d]);
+        cG[d] = (ACT == kAll && h == 0) ? t.Kpp * t.z[d] : pk_fma(t.Kpp, t.z[d], cG[d]);
+        if (DIV) cZ[d] = (ACT == kAll && h == 0) ? t.K * t.z[d] : pk_fma(t.K, t.z[d], cZ[d]);
       }
     }
 #pragma unroll
@@ -1195,9 +1359,13 @@ __device__ __forceinline__ void sym_fwd_pkn_body(const Args& a, const Scal& sc, 
 #pragma unroll
     for (int k = 0; k < W; ++k) racc[h][k] = splat(0.f);
 
-  CutBox<D> rbox;
+  constexpr bool kRowPair = CUT && kCutRowPair;
+  CutBox<D> rbox, rpbox[NRP];
   const int nB = cut_tiles(M);
-  if constexpr (CUT) cut_row_box<D, G / 64>(boxes, __builtin_amdgcn_readfirstlane(A) * (G / 64), nB, rbox);
+  if constexpr (kRowPair)
+    cut_rowpair_boxes<D, NRP>(boxes, __builtin_amdgcn_readfirstlane(A) * (G / 64), nB, rpbox);
+  else if constexpr (CUT)
+    cut_row_box<D, G / 64>(boxes, __builtin_amdgcn_readfirstlane(A) * (G / 64), nB, rbox);
 
   auto stage = [&](int B, int buf) {
 #pragma unroll
@@ -1241,7 +1409,12 @@ __device__ __forceinline__ void sym_fwd_pkn_body(const Args& a, const Scal& sc, 
     const bool diag = A == B;
     unsigned far = 0;
     if constexpr (CUT) {
-      if (sym) far = cut_mask<D, G / 64>(boxes, rbox, B, nB, T);
+      if (sym) {
+        if constexpr (kRowPair)
+          far = cut_mask_rowpair<D, G / 64, NRP>(boxes, rpbox, B, nB, T);
+        else
+          far = cut_mask<D, G / 64>(boxes, rbox, B, nB, T);
+      }
     }
 #pragma unroll 1
     for (int h = 0; h < G / 64; ++h) {   // 64-column slices of the group
@@ -1249,16 +1422,35 @@ __device__ __forceinline__ void sym_fwd_pkn_body(const Args& a, const Scal& sc, 
         float cacc[W];
 #pragma unroll
         for (int k = 0; k < W; ++k) cacc[k] = 0.f;
-        if (sym && !((far >> h) & 1u)) {
+        // DICP_CUT_ROWPAIR: the wave's active row pairs against slice h (wave-uniform) choose
+        // the loop body; otherwise the one loop, kept as it was
+        unsigned act = P::kAll;
+        if constexpr (kRowPair) act = ~(far >> (NRP * h)) & P::kAll;
+        if (sym && (kRowPair ? act != 0u : !((far >> h) & 1u))) {
+          if constexpr (kRowPair) {
+            cut_dispatch<P::kAll>(act, [&](auto ac) {
 #pragma unroll 1
-          for (int k2 = 0; k2 < 64; ++k2) {
-            const int col = h * 64 + ((l + k2) & 63);
-            float rec[4 * CW + NP];
-            ldrec(col, rec);
-            float ct[W];
-            P::pair_sym(row, rec, racc, ct);
+              for (int k2 = 0; k2 < 64; ++k2) {
+                const int col = h * 64 + ((l + k2) & 63);
+                float rec[4 * CW + NP];
+                ldrec(col, rec);
+                float ct[W];
+                P::template pair_sym<decltype(ac)::value>(row, rec, racc, ct);
 #pragma unroll
-            for (int k = 0; k < W; ++k) cacc[k] = rol1(cacc[k]) + ct[k];
+                for (int k = 0; k < W; ++k) cacc[k] = rol1(cacc[k]) + ct[k];
+              }
+            });
+          } else {
+#pragma unroll 1
+            for (int k2 = 0; k2 < 64; ++k2) {
+              const int col = h * 64 + ((l + k2) & 63);
+              float rec[4 * CW + NP];
+              ldrec(col, rec);
+              float ct[W];
+              P::pair_sym(row, rec, racc, ct);
+#pragma unroll
+              for (int k = 0; k < W; ++k) cacc[k] = rol1(cacc[k]) + ct[k];
+            }
           }
 #pragma unroll
           for (int k = 0; k < W; ++k) cacc[k] = rol1(cacc[k]);
