@@ -29,6 +29,8 @@ FLOPS_PER_PAIR = {
     "GMM_ESTEP": 2 * 13 + 12,  # two sweeps (max, then exp + 6 weighted sums)
     "GMM_MSTEP": 2 * 13 + 6,
     "GMM_TARGETS": 30,
+    "GMM_ESTEP_NOSTATS": 12,  # 3 sub + 4 fma + the sum of the exps (+ 1 exp)
+    "GMM_ASSIGN_K1": 13, "GMM_ASSIGN_K4": 13,   # 3 sub + mul + 3 fma, compare / select; no exp
 }
 # HBM bytes per launch (algorithmic: each input read once, each output written once).
 
@@ -130,6 +132,30 @@ def main():
             rep(f"GMM_MSTEP@{N}x{C}", t, N * C, 4 * (4 * N + 4 * C + 4 * C))
             t = timed(lambda: _lib.gmm_targets(X, T2, mu, w2, 0.05, mu, w2), reps=5)
             rep(f"GMM_TARGETS@{N}x{C}", t, N * C, 4 * (4 * N + 9 * C + 7 * N))
+    if only is None or "ASSIGN" in only:
+        # the top-k correspondence pass next to its yardstick, the stats-less E-step (the same
+        # pair count plus an exp), 100 back-to-back launches each, alternated three times so the
+        # lines show the spread; then the whole GaussianMixtureUnif.assign call (that E-step +
+        # the top-k pass + O(N k) torch)
+        from difficp_amd.core.GMM import GaussianMixtureUnif
+        N = C = n_big
+        X = torch.rand(N, D, device=dev)
+        mu = torch.rand(C, D, device=dev)
+        G = GaussianMixtureUnif(mu, sigma=0.05, spec={"device": dev, "dtype": torch.float32})
+        _, w2, mu2 = G._columns(G.mu, G.w)
+        nbytes = 4 * (4 * N + 4 * C)
+        for _ in range(3):
+            t = timed(lambda: _lib.gmm_estep(X, mu, w2, mu2, 0.05, 0.0, False), reps=100)
+            rep(f"GMM_ESTEP_NOSTATS@{N}x{C}", t, N * C, nbytes + 8 * N,
+                {"splits": _lib.num_splits(_lib.WS_GMM_ESTEP, N, C)})
+            for K in (1, 4):
+                t = timed(lambda: _lib.gmm_assign(X, mu, w2, 0.05, K), reps=100)
+                rep(f"GMM_ASSIGN_K{K}@{N}x{C}", t, N * C, nbytes + 8 * N * K,
+                    {"splits": _lib.num_splits(_lib.WS_GMM_ASSIGN, N, C), "Texp_per_s": 0.0,
+                     "frac_exp_peak": 0.0})
+        for K in (1, 4):
+            t = timed(lambda: G.assign(X, k=K), reps=100)
+            rep(f"API_ASSIGN_K{K}@{N}x{C}", t, N * C, 2 * nbytes + 8 * N * (K + 1))
     if args.out:
         with open(args.out, "w") as f:
             json.dump(results, f, indent=1)

@@ -24,7 +24,7 @@ KBASE, KREDSCAL, KRED, GRADK, GRADK_REV, DDK, GENDK, HESSK, LAPK, GRADLAPK, GRAD
 # enum dicp_ws_kind
 WS_RED, WS_ODE_SELF_FWD, WS_ODE_SELF_BWD, WS_ODE_EXT_FWD, WS_ODE_EXT_BWD, WS_GMM_ESTEP, \
     WS_GMM_MSTEP, WS_GMM_TARGETS, WS_RIDGE_CG, WS_ODE_SELF_FWD_ROWS, WS_ODE_SELF_BWD_PART, WS_GRAD, \
-    WS_ODE_SELF_FWD_PHASED = range(13)
+    WS_ODE_SELF_FWD_PHASED, WS_GMM_ASSIGN = range(14)
 # enum dicp_grad_kind
 GRAD_HESSW, GRAD_HESSWP, GRAD_ZDOTV, GRAD_HESS3, GRAD_GRADLAP3 = range(5)
 
@@ -52,6 +52,7 @@ _SIGNATURES = {
     "dicp_gmm_estep_hint_f32": [_P, _I64, _P, _P, _P, _I64, _INT, _DBL, _DBL, _P, _P, _P, _P, _P, _SZ, _P],
     "dicp_gmm_mstep_f32": [_P, _P, _I64, _P, _P, _I64, _INT, _DBL, _P, _P, _SZ, _P],
     "dicp_gmm_targets_f32": [_P, _P, _I64, _P, _P, _DBL, _P, _P, _I64, _INT, _P, _P, _SZ, _P],
+    "dicp_gmm_assign_f32": [_P, _I64, _P, _P, _I64, _INT, _DBL, _INT, _P, _P, _P, _SZ, _P],
     "dicp_lddmm_ode_self_fwd_rows_f32": [_P, _P, _I64, _I64, _I64, _INT, _DBL, _DBL, _P, _P, _P, _P,
                                          _P, _SZ, _P],
     "dicp_lddmm_euler_step_rows_f32": [_P, _P, _I64, _I64, _I64, _INT, _DBL, _DBL, _DBL, _P, _P, _P,
@@ -303,6 +304,8 @@ FLOPS_PER_PAIR = {
     "gauss_red": 15, "ode_self_fwd": 33, "ode_self_fwd_eta": 70, "ode_self_bwd": 70, "ode_self_bwd_eta": 120,
     "ode_ext_fwd": 22, "ode_ext_bwd": (36 + 49) / 2, "gmm_estep": 37, "gmm_mstep": 31,
     "gmm_targets": 32, "ridge_cg": 15,
+    # 3 sub + mul + 3 fma and the compare / select of the running best; no exp
+    "gmm_assign": 13,
 }
 # Executed fp32 arithmetic per ordered pair where it differs from the algorithmic figure
 # (FMA = 2 flop, from the hot loop's instruction counts, tools/isa_loop_stats.py): the
@@ -867,6 +870,34 @@ def gmm_targets(X, T2, mu_old, w2_old, sigma_old: float, mu_new, lpi_new):
                                     _ptr(rows), _ptr(ws), nb, _stream(X.device)))
     _check_rc(rc, "gmm_targets")
     return rows
+
+
+def gmm_assign(rows, cols, bias, sigma: float, k: int = 1):
+    """Biased top-k row reduction (dicp_gmm_assign_f32): for every row i the k largest
+    val_ij = bias_j - log2(e) |rows_i - cols_j|^2 / (2 sigma^2) over the columns j, in descending
+    order (equal values by increasing column).  bias: (N,) float32 in the log2 domain, or None
+    (zeros).  Returns (idx int32 (M, k), val float32 (M, k)); unfilled slots hold -1 / -inf, a
+    row with a non-finite coordinate -1 / NaN."""
+    rows = _dev(rows, "rows")
+    cols = _dev(cols, "cols")
+    M, D = rows.shape
+    N = cols.shape[0]
+    if cols.shape[1] != D:
+        raise ValueError(f"gmm_assign: rows are {D}-dimensional, cols {cols.shape[1]}-dimensional")
+    if bias is not None:
+        bias = _dev(bias, "bias")
+        if bias.shape != (N,):
+            raise ValueError(f"gmm_assign: bias must be shaped ({N},)")
+    k = int(k)
+    dev = rows.device
+    idx = torch.empty((M, k), device=dev, dtype=torch.int32)
+    val = torch.empty((M, k), device=dev, dtype=torch.float32)
+    ws, nb = (None, 0) if M == 0 else _workspace(WS_GMM_ASSIGN, M, N, D, dev)
+    rc = _launch("gmm_assign", M * N, 4 * ((M + N) * (D + 1) + 2 * M * k),
+                 lambda: lib().dicp_gmm_assign_f32(_ptr(rows), M, _ptr(cols), _ptr(bias), N, D, float(sigma),
+                                                   k, _ptr(idx), _ptr(val), _ptr(ws), nb, _stream(dev)))
+    _check_rc(rc, "gmm_assign")
+    return idx, val
 
 
 # ---------------------------------------------------------------------------------------

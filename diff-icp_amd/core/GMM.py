@@ -19,6 +19,7 @@ all_gather and combined in rank order, so every rank holds bit-identical paramet
 """
 from __future__ import annotations
 
+import collections
 import copy
 import os
 import math
@@ -37,6 +38,10 @@ from ..tools.spec import defspec
 _HINT_ANY = os.environ.get("DICP_ESTEP_HINT_ANY", "0") != "0"
 
 _LOG2E = 1.4426950408889634
+_LN2 = 0.6931471805599453
+
+# GaussianMixtureUnif.assign's result: index (N, k) int64, log_resp (N, k), log_outlier (N,) or None
+Assignment = collections.namedtuple("Assignment", ["index", "log_resp", "log_outlier"])
 
 
 def _comm_active(comm):
@@ -206,6 +211,57 @@ class GaussianMixtureUnif(torch.nn.Module):
         Zw = w.logsumexp(dim=0)
         lpi = (w - Zw).contiguous()
         return lpi, (lpi * _LOG2E).contiguous(), (mu * mu).sum(-1).contiguous()
+
+    # ------------------------------------------------------------------------------------
+    # Hard / top-k correspondences (no reference counterpart: log_responsibilities is dense)
+    def _row_lse(self, X):
+        """(X on the model's spec, mu, w2, T, T2) of one stats-less E-step; no state touched
+        (in particular not the EM loop's _estep_hint)."""
+        X = X.detach().to(**self.spec).contiguous()
+        mu = self.mu.detach().contiguous()
+        _, w2, mu2 = self._columns(mu, self.w.detach())
+        sigma = float(self.sigma)
+        lgn = self.D * (np.log(sigma) + 0.5 * np.log(2 * math.pi))
+        T, T2, _ = _lib.gmm_estep(X, mu, w2, mu2, sigma, lgn, False)
+        return X, mu, w2, T, T2
+
+    def assign(self, X, k=1):
+        """For each point of X (N, D) the k components of largest responsibility, at any size
+        (one E-step and one fused top-k pass, csrc/assign.hip; nothing N x C is formed).
+        Returns Assignment(index, log_resp, log_outlier):
+          index (N, k) int64, by decreasing responsibility (ties: the smaller component index);
+              -1 in slots that cannot be filled (fewer than k live components; a NaN point)
+          log_resp (N, k): log responsibility among the components, the values of
+              log_responsibilities(X)[n, index] (-inf in unfilled slots)
+          log_outlier (N,): log posterior of the outlier class (the E-step's lgamma0_n), None
+              for a mixture without outliers; ValueError if vol0 is unset (see set_vol0).
+        Inputs are detached; the model is not changed."""
+        if self.outliers is not None and self.outliers["vol0"] is None:
+            raise ValueError("assign: the outlier reference volume vol0 is not set (set_vol0)")
+        X, mu, w2, T, T2 = self._row_lse(X)
+        idx, val = _lib.gmm_assign(X, mu, w2, float(self.sigma), k)
+        log_resp = _LN2 * (val - T2[:, None])
+        log_outlier = None
+        if self.outliers is not None:
+            eta0_n = self.outliers["eta0"] - np.log(self.outliers["vol0"]) - T
+            log_outlier, _ = self.log_ratio_to_proba(eta0_n)
+        return Assignment(idx.long(), log_resp, log_outlier)
+
+    def nearest_points(self, X, k=1):
+        """The other direction, through the same kernel: for each component c the k points of X
+        of largest responsibility gamma_nc (normalised over the components, per point).
+        Returns (index (C, k) int64, log_resp (C, k) = log gamma[index, c]), by decreasing
+        responsibility (ties: the smaller point index); -1 / -inf in unfilled slots and for a
+        dead component (w = -inf).  Inputs are detached; the model is not changed.  Under a
+        communicator (a sharded atlas) X is this rank's points: the answer is over the local
+        rows only, nothing is exchanged."""
+        X, mu, w2, _, T2 = self._row_lse(X)
+        # a point without a finite LSE (NaN coordinates) is never returned
+        bias = torch.where(torch.isfinite(T2), -T2, torch.full_like(T2, float("-inf")))
+        idx, val = _lib.gmm_assign(mu, X, bias, float(self.sigma), k)
+        log_resp = _LN2 * (val + w2[:, None])
+        dead = torch.isinf(w2)[:, None].expand_as(idx)
+        return torch.where(dead, torch.full_like(idx, -1), idx).long(), log_resp
 
     # ------------------------------------------------------------------------------------
     def EM_step_hip(self, X, skip_M=False):

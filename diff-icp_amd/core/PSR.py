@@ -20,7 +20,7 @@ import copy
 import numpy as np
 import torch
 
-from .GMM import GaussianMixtureUnif, _comm_active, _gather_rows, _sum_ranks
+from .GMM import Assignment, GaussianMixtureUnif, _comm_active, _gather_rows, _sum_ranks
 from .LDDMM import LDDMMModel
 from .registrations import LDDMMRegistration
 from ..tools.in_out import read_point_sets
@@ -131,6 +131,23 @@ class MultiPSR:
 
     def get_template(self, s=0):
         return self.GMMi[s].mu
+
+    def correspondences(self, k=0, s=0, topk=1, direction="data"):
+        """Hard / top-k correspondences between the warped points x1[k, s] and the template
+        GMMi[s] (no reference counterpart).  direction "data": for each point its topk components,
+        GaussianMixtureUnif.assign's Assignment(index, log_resp, log_outlier); "template": for each
+        component its topk points of frame k, nearest_points' (index, log_resp).  Computed on the
+        compute spec, returned on the data spec; changes no state."""
+        if direction not in ("data", "template"):
+            raise ValueError(f"unknown direction : {direction}. Choices are 'data' or 'template'")
+        X = self.x1[k, s].to(**self.compspec)
+        dev = self.dataspec["device"]
+        if direction == "data":
+            a = self.GMMi[s].assign(X, k=topk)
+            lo = None if a.log_outlier is None else a.log_outlier.to(**self.dataspec)
+            return Assignment(a.index.to(dev), a.log_resp.to(**self.dataspec), lo)
+        index, log_resp = self.GMMi[s].nearest_points(X, k=topk)
+        return index.to(dev), log_resp.to(**self.dataspec)
 
     # ------------------------------------------------------------------------------------
     def _assign_targets(self, s, allys):

@@ -13,6 +13,8 @@ int dicp_lddmm_splits(int kind, int64_t M, int64_t N);
 size_t dicp_gmm_ws(int kind, int64_t M, int64_t N, int D);
 size_t dicp_solve_ws(int kind, int64_t M, int D);
 size_t dicp_grad_ws(int64_t M, int64_t N, int D);
+size_t dicp_assign_ws(int64_t M, int64_t N, int D);
+int dicp_assign_splits(int64_t M, int64_t N);
 
 namespace {
 thread_local char g_err[512] = "";
@@ -48,6 +50,8 @@ extern "C" size_t dicp_workspace_bytes(int kind, int64_t M, int64_t N, int D) {
   size_t b = 0;
   if (kind == DICP_WS_GRAD)
     b = dicp_grad_ws(M, N, D);
+  else if (kind == DICP_WS_GMM_ASSIGN)
+    b = dicp_assign_ws(M, N, D);
   else if (kind == DICP_WS_RIDGE_CG)
     b = dicp_solve_ws(kind, M, D);
   else if (kind >= DICP_WS_GMM_ESTEP && kind <= DICP_WS_GMM_TARGETS)
@@ -59,6 +63,7 @@ extern "C" size_t dicp_workspace_bytes(int kind, int64_t M, int64_t N, int D) {
 }
 
 extern "C" int dicp_num_splits(int kind, int64_t M, int64_t N) {
+  if (kind == DICP_WS_GMM_ASSIGN) return dicp_assign_splits(M, N);
   return dicp_lddmm_splits(kind, M, N);
 }
 

@@ -348,6 +348,23 @@ int dicp_gmm_targets_f32(const float* X, const float* T2, int64_t N, const float
                          const float* lpi_new, int64_t C, int D, float* rows, void* ws,
                          size_t ws_bytes, dicp_stream_t stream);
 
+/* Hard / top-K correspondences (no reference counterpart: the reference only has the dense
+ * (N, C) log_responsibilities, GMM.py:221-232): a biased top-K row reduction
+ *   val_ij = bias_j - k2 |rows_i - cols_j|^2,   k2 = log2(e) / (2 sigma^2)   (log2 domain)
+ * rows (M, D), cols (N, D), bias (N,) or NULL (reads as 0); D = 2 or 3, K = 1..4.
+ *   idx (M, K) int32, val (M, K): the K largest val_ij of row i, in descending order; equal
+ *   values in increasing column index.  Bitwise reproducible, independent of the column split.
+ * The squared distance is formed from the coordinate differences.  A column whose val is -inf
+ * (bias = -inf: a dead component) or NaN is never returned; slots that cannot be filled hold
+ * idx = -1, val = -inf; a row with a non-finite coordinate holds idx = -1, val = NaN throughout.
+ * Points -> components: rows = X, cols = mu, bias = w2 (val - T2_n = log2 responsibility).
+ * Components -> points: rows = mu, cols = X, bias = -T2 (the row constant w2_c is the caller's).
+ * M = 0 launches nothing; N = 0 fills the outputs as above.  Any other D or K: DICP_ERR_INVALID.
+ * Workspace kind DICP_WS_GMM_ASSIGN (M = rows, N = columns; sized for K = 4).  Not batchable. */
+int dicp_gmm_assign_f32(const float* rows, int64_t M, const float* cols, const float* bias, int64_t N,
+                        int D, double sigma, int K, int32_t* idx, float* val,
+                        void* ws, size_t ws_bytes, dicp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Momenta from speeds (LDDMMModel.v2p, LDDMM.py:235-253): ridge solve
  *   (K(x,x) + alpha I) b = v,   x (M,D), v, b (M,D)
@@ -397,7 +414,8 @@ enum dicp_ws_kind {
   DICP_WS_ODE_SELF_FWD_ROWS = 9, /* M = rows of the slice, N = all points (columns) */
   DICP_WS_ODE_SELF_BWD_PART = 10, /* M = points, N = nparts */
   DICP_WS_GRAD = 11,             /* dicp_gauss_red_grad_f32: M rows, N columns */
-  DICP_WS_ODE_SELF_FWD_PHASED = 12 /* dicp_lddmm_euler_step_phase_f32: M = rows, N = points */
+  DICP_WS_ODE_SELF_FWD_PHASED = 12, /* dicp_lddmm_euler_step_phase_f32: M = rows, N = points */
+  DICP_WS_GMM_ASSIGN = 13        /* dicp_gmm_assign_f32: M = rows, N = columns */
 };
 size_t dicp_workspace_bytes(int kind, int64_t M, int64_t N, int D);
 
