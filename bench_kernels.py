@@ -31,6 +31,8 @@ FLOPS_PER_PAIR = {
     "GMM_TARGETS": 30,
     "GMM_ESTEP_NOSTATS": 12,  # 3 sub + 4 fma + the sum of the exps (+ 1 exp)
     "GMM_ASSIGN_K1": 13, "GMM_ASSIGN_K4": 13,   # 3 sub + mul + 3 fma, compare / select; no exp
+    "ODE_EXT_FWD": 22,        # v and the divergence row (eta = 0): 3 sub + mul + 7 fma
+    "EXT_JAC": 35, "EXT_JAC_STEP": 35,   # v and the D x D gradient (eta = 0): 3 sub + 4 mul + 3 add + 12 fma
 }
 # HBM bytes per launch (algorithmic: each input read once, each output written once).
 
@@ -156,6 +158,53 @@ def main():
         for K in (1, 4):
             t = timed(lambda: G.assign(X, k=K), reps=100)
             rep(f"API_ASSIGN_K{K}@{N}x{C}", t, N * C, 2 * nbytes + 8 * N * (K + 1))
+    if only is None or "EXT_JAC" in only:
+        # the velocity-gradient pass (csrc/ext_jac.hip) next to its yardstick, the external-point
+        # forward with the divergence row, at the same N x M: back-to-back launches, alternated
+        # three times so the lines show the spread -- on the default dispatch (the forward may take
+        # the centred expansion) and with red_alg 0 / ext_alg 1 (both on the packed row skeleton);
+        # then a 10-step flow_jacobian next to apply
+        from difficp_amd.core.LDDMM import LDDMMModel
+        from difficp_amd.core.registrations import LDDMMRegistration
+        for (N, M) in [(n_big, n_big), (n_big, n_big // 5)]:
+            x = torch.rand(N, D, device=dev)
+            q = torch.rand(M, D, device=dev)
+            p = 0.01 * torch.randn(M, D, device=dev)
+            G = 0.1 * torch.randn(N, D, D, device=dev)
+            nb = 4 * (3 * N + 6 * M)
+            for mode, opts in (("default", {}), ("packed", {"red_alg": 0, "ext_alg": 1})):
+                old = {k: _lib.get_option(k) for k in opts}
+                for k, v in opts.items():
+                    _lib.set_option(k, v)
+                try:
+                    for _ in range(3):
+                        for eta in (0.0, 2e-3):
+                            ex = {"dispatch": mode, "eta": eta}
+                            t = timed(lambda: _lib.ode_ext_fwd(x, q, p, 0.1, eta, True), reps=50)
+                            rep(f"ODE_EXT_FWD@{N}x{M}", t, N * M, nb + 16 * N,
+                                dict(ex, splits=_lib.num_splits(_lib.WS_ODE_EXT_FWD, M, N)))
+                            t = timed(lambda: _lib.ode_ext_jac(x, q, p, 0.1, eta), reps=50)
+                            rep(f"EXT_JAC@{N}x{M}", t, N * M, nb + 48 * N,
+                                dict(ex, splits=_lib.num_splits(_lib.WS_ODE_EXT_JAC, M, N)))
+                    t = timed(lambda: _lib.ext_jac_step(x, G, q, p, 0.1, 0.0, 0.1), reps=50)
+                    rep(f"EXT_JAC_STEP@{N}x{M}", t, N * M, nb + 84 * N, {"dispatch": mode, "eta": 0.0})
+                finally:
+                    for k, v in old.items():
+                        _lib.set_option(k, v)
+        N = M = n_big
+        LM = LDDMMModel(sigma=0.1, D=D, lambd=100.0, version="hybrid", scheme="Euler", nt=10,
+                        spec={"device": dev, "dtype": torch.float32})
+        reg = LDDMMRegistration(LM, torch.rand(M, D, device=dev), 0.001 * torch.randn(M, D, device=dev))
+        X = torch.rand(N, D, device=dev)
+        sh = reg.shoot(None)
+        for _ in range(3):
+            LM.shoot_cache.clear()
+            t = timed(lambda: (LM.shoot_cache.clear(), reg.apply(X)), warm=1, reps=5)
+            rep(f"API_APPLY@{N}x{M}", t, 10 * N * M, 0)
+            t = timed(lambda: reg.apply_with_jacobian(X), warm=1, reps=5)
+            rep(f"API_APPLY_WITH_JACOBIAN@{N}x{M}", t, 10 * N * M, 0)
+            t = timed(lambda: LM.flow_jacobian(reg.q0, reg.a0, X, shoot=sh), warm=1, reps=5)
+            rep(f"API_FLOW_JACOBIAN_GIVEN_SHOOT@{N}x{M}", t, 10 * N * M, 0)
     if args.out:
         with open(args.out, "w") as f:
             json.dump(results, f, indent=1)

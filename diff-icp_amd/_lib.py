@@ -24,7 +24,7 @@ KBASE, KREDSCAL, KRED, GRADK, GRADK_REV, DDK, GENDK, HESSK, LAPK, GRADLAPK, GRAD
 # enum dicp_ws_kind
 WS_RED, WS_ODE_SELF_FWD, WS_ODE_SELF_BWD, WS_ODE_EXT_FWD, WS_ODE_EXT_BWD, WS_GMM_ESTEP, \
     WS_GMM_MSTEP, WS_GMM_TARGETS, WS_RIDGE_CG, WS_ODE_SELF_FWD_ROWS, WS_ODE_SELF_BWD_PART, WS_GRAD, \
-    WS_ODE_SELF_FWD_PHASED, WS_GMM_ASSIGN = range(14)
+    WS_ODE_SELF_FWD_PHASED, WS_GMM_ASSIGN, WS_ODE_EXT_JAC = range(15)
 # enum dicp_grad_kind
 GRAD_HESSW, GRAD_HESSWP, GRAD_ZDOTV, GRAD_HESS3, GRAD_GRADLAP3 = range(5)
 
@@ -48,6 +48,8 @@ _SIGNATURES = {
     "dicp_lddmm_ode_ext_fwd_f32": [_P, _I64, _P, _P, _I64, _INT, _DBL, _DBL, _P, _P, _P, _SZ, _P],
     "dicp_lddmm_ode_ext_bwd_f32": [_P, _I64, _P, _P, _I64, _INT, _DBL, _DBL, _P, _P, _P, _P, _P,
                                    _P, _SZ, _P],
+    "dicp_lddmm_ode_ext_jac_f32": [_P, _I64, _P, _P, _I64, _INT, _DBL, _DBL, _P, _P, _P, _SZ, _P],
+    "dicp_lddmm_ext_jac_step_f32": [_P, _P, _I64, _P, _P, _I64, _INT, _DBL, _DBL, _DBL, _P, _P, _P, _SZ, _P],
     "dicp_gmm_estep_f32": [_P, _I64, _P, _P, _P, _I64, _INT, _DBL, _DBL, _P, _P, _P, _P, _SZ, _P],
     "dicp_gmm_estep_hint_f32": [_P, _I64, _P, _P, _P, _I64, _INT, _DBL, _DBL, _P, _P, _P, _P, _P, _SZ, _P],
     "dicp_gmm_mstep_f32": [_P, _P, _I64, _P, _P, _I64, _INT, _DBL, _P, _P, _SZ, _P],
@@ -306,6 +308,9 @@ FLOPS_PER_PAIR = {
     "gmm_targets": 32, "ridge_cg": 15,
     # 3 sub + mul + 3 fma and the compare / select of the running best; no exp
     "gmm_assign": 13,
+    # velocity gradient at carried points (csrc/ext_jac.hip), eta = 0: 3 sub + 3 fma + mul, one
+    # exp2, 3 mul + 3 add + 9 fma
+    "ode_ext_jac": 35,
 }
 # Executed fp32 arithmetic per ordered pair where it differs from the algorithmic figure
 # (FMA = 2 flop, from the hot loop's instruction counts, tools/isa_loop_stats.py): the
@@ -772,6 +777,59 @@ def ode_ext_fwd(x, q, p, sigma: float, eta: float, want_div: bool):
                                           _stream(x.device)))
     _check_rc(rc, "ode_ext_fwd")
     return vx, gx
+
+
+def _jac_args(x, q, p, what):
+    x = _dev(x, "x")
+    q = _dev(q, "q")
+    p = _dev(p, "p")
+    if x.dim() != 2 or q.dim() != 2 or q.shape[1] != x.shape[1] or p.shape != q.shape:
+        raise ValueError(f"{what}: x (N, D), q and p (M, D) expected, got {tuple(x.shape)}, "
+                         f"{tuple(q.shape)}, {tuple(p.shape)}")
+    return x, q, p
+
+
+def ode_ext_jac(x, q, p, sigma: float, eta: float):
+    """Velocity and velocity gradient at the carried points x (dicp_lddmm_ode_ext_jac_f32):
+    returns (vx (N, D), A (N, D, D)) with A[i, d, a] = dv_d/dx_a (x_i)."""
+    x, q, p = _jac_args(x, q, p, "ode_ext_jac")
+    N, D = x.shape
+    M = q.shape[0]
+    vx = torch.empty_like(x)
+    A = torch.empty((N, D, D), device=x.device, dtype=torch.float32)
+    if N == 0:
+        return vx, A
+    ws, nb = _workspace(WS_ODE_EXT_JAC, M, N, D, x.device)
+    rc = _launch("ode_ext_jac", N * M, 4 * (N * (2 * D + D * D) + 2 * M * D),
+                 lambda: lib().dicp_lddmm_ode_ext_jac_f32(_ptr(x), N, _ptr(q), _ptr(p), M, D, float(sigma),
+                                                          float(eta), _ptr(vx), _ptr(A), _ptr(ws), nb,
+                                                          _stream(x.device)))
+    _check_rc(rc, "ode_ext_jac")
+    return vx, A
+
+
+def ext_jac_step(x, G, q, p, sigma: float, eta: float, dt: float):
+    """One Euler step of the carried points and of the displacement gradient G = J - I of their
+    discrete flow (dicp_lddmm_ext_jac_step_f32): x_next = x + dt v(x), G_next = G + dt A (I + G).
+    G: (N, D, D) or None (zero).  Returns new tensors (x_next, G_next)."""
+    x, q, p = _jac_args(x, q, p, "ext_jac_step")
+    N, D = x.shape
+    M = q.shape[0]
+    if G is not None:
+        G = _dev(G, "G")
+        if G.shape != (N, D, D):
+            raise ValueError(f"ext_jac_step: G must be shaped ({N}, {D}, {D})")
+    xn = torch.empty_like(x)
+    Gn = torch.empty((N, D, D), device=x.device, dtype=torch.float32)
+    if N == 0:
+        return xn, Gn
+    ws, nb = _workspace(WS_ODE_EXT_JAC, M, N, D, x.device)
+    rc = _launch("ode_ext_jac", N * M, 4 * (2 * N * (D + D * D) + 2 * M * D),
+                 lambda: lib().dicp_lddmm_ext_jac_step_f32(_ptr(x), _ptr(G), N, _ptr(q), _ptr(p), M, D,
+                                                           float(sigma), float(eta), float(dt), _ptr(xn),
+                                                           _ptr(Gn), _ptr(ws), nb, _stream(x.device)))
+    _check_rc(rc, "ext_jac_step")
+    return xn, Gn
 
 
 def ode_ext_bwd(x, q, p, gvx, gdiv, sigma: float, eta: float, gq, gp):

@@ -374,6 +374,67 @@ class LDDMMModel:
             shoot.q0_key = None
         return shoot
 
+    # ------------------------------------------------------------------------------------
+    # Deformation Jacobian at carried points (extension; csrc/ext_jac.hip)
+    def Dv(self, x, q, p):
+        """Velocity gradient A[i, d, a] = dv_d/dx_a (x_i) of the field of (q, p), (N, D, D);
+        its trace is minus the divergence row of the external-point ODE.  Inputs are detached."""
+        getspec(x, q, p)
+        return _lib.ode_ext_jac(x.detach(), q.detach(), p.detach(), self.Kernel.sigma, float(self.eta))[1]
+
+    def _support_states(self, q0, p0, need_p1=False):
+        """(Q, P) of Shoot(q0, p0), without reading or writing the model's shoot_cache (need_p1
+        False: the final momenta may be left unformed, as in Shoot)."""
+        q0c = q0.contiguous()
+        with torch.no_grad():
+            Q, P, _, _ = ShootFn.apply(q0c, p0.contiguous(), None, self.Kernel.sigma, float(self.eta),
+                                       int(self.nt), self.scheme, bool(self.withlogdet), self.row_split,
+                                       getattr(self, "row_orders", None), None, bool(need_p1),
+                                       self._raw_for(q0))
+        return Q, P
+
+    def flow_jacobian(self, q0, p0, x0, shoot=None):
+        """The carried points x1 = phi(x0) of Shoot(q0, p0, x0) and the Jacobian J_i = d phi(x_i) /
+        d x_i of that DISCRETE flow (the exact derivative of what the shooting computes), (N, D, D).
+        The displacement gradient G = J - I is what the steps carry (entries of J near 1 would lose
+        ~6e-8 per step to rounding); J = I + G is formed once at the end.
+        Euler: one fused step (x, G) -> (x + dt v, G + dt A (I + G)) per time step; Ralston: the
+        two stages' A1 at (x; S_t) and A2 at (x_m; S_m), S_m = S_t + (2 dt / 3) ODE(S_t).
+        shoot: a forward shoot of (q0, p0) (with or without carried points) whose support states
+        are reused; None: they are computed here.  Inputs are detached; the model (its
+        shoot_cache included) is left as it was."""
+        getspec(q0, p0, x0)
+        q0, p0, x0 = q0.detach(), p0.detach(), x0.detach()
+        if shoot is None:
+            Q, P = self._support_states(q0, p0)
+        else:
+            Q, P = shoot.Q.detach(), shoot.P.detach()
+        nt = Q.shape[0] - 1
+        sigma, eta, dt = self.Kernel.sigma, float(self.eta), 1.0 / nt
+        D = x0.shape[1]
+        x, G = x0.contiguous(), None
+        raw = self._raw_for(q0)
+        with torch.no_grad():
+            if self.scheme == "Euler":
+                for t in range(nt):
+                    x, G = _lib.ext_jac_step(x, G, Q[t], P[t], sigma, eta, dt)
+            else:
+                I = torch.eye(D, device=x.device, dtype=x.dtype)
+                G = torch.zeros((x.shape[0], D, D), device=x.device, dtype=x.dtype)
+                for t in range(nt):
+                    q, p = Q[t], P[t]
+                    v1, A1 = _lib.ode_ext_jac(x, q, p, sigma, eta)
+                    with _lib.coord_mode(raw):
+                        vq, mG = _lib.ode_self_fwd(q, p, sigma, eta, False)[:2]
+                    qm, pm = q + (2 * dt / 3) * vq, p + (2 * dt / 3) * mG
+                    B1 = A1 @ (I + G)
+                    v2, A2 = _lib.ode_ext_jac(x + (2 * dt / 3) * v1, qm, pm, sigma, eta)
+                    B2 = A2 @ (I + G + (2 * dt / 3) * B1)
+                    x = x + (dt / 4) * v1 + (3 * dt / 4) * v2
+                    G = G + (dt / 4) * B1 + (3 * dt / 4) * B2
+            J = G + torch.eye(D, device=x.device, dtype=x.dtype)
+        return x, J
+
     def BasicQuadLossFunctor(self, y, cmul=1):
         y = y.detach()
 

@@ -15,6 +15,8 @@ size_t dicp_solve_ws(int kind, int64_t M, int D);
 size_t dicp_grad_ws(int64_t M, int64_t N, int D);
 size_t dicp_assign_ws(int64_t M, int64_t N, int D);
 int dicp_assign_splits(int64_t M, int64_t N);
+size_t dicp_ext_jac_ws(int64_t M, int64_t N, int D);
+int dicp_ext_jac_splits(int64_t M, int64_t N);
 
 namespace {
 thread_local char g_err[512] = "";
@@ -52,6 +54,8 @@ extern "C" size_t dicp_workspace_bytes(int kind, int64_t M, int64_t N, int D) {
     b = dicp_grad_ws(M, N, D);
   else if (kind == DICP_WS_GMM_ASSIGN)
     b = dicp_assign_ws(M, N, D);
+  else if (kind == DICP_WS_ODE_EXT_JAC)
+    b = dicp_ext_jac_ws(M, N, D);
   else if (kind == DICP_WS_RIDGE_CG)
     b = dicp_solve_ws(kind, M, D);
   else if (kind >= DICP_WS_GMM_ESTEP && kind <= DICP_WS_GMM_TARGETS)
@@ -64,6 +68,7 @@ extern "C" size_t dicp_workspace_bytes(int kind, int64_t M, int64_t N, int D) {
 
 extern "C" int dicp_num_splits(int kind, int64_t M, int64_t N) {
   if (kind == DICP_WS_GMM_ASSIGN) return dicp_assign_splits(M, N);
+  if (kind == DICP_WS_ODE_EXT_JAC) return dicp_ext_jac_splits(M, N);
   return dicp_lddmm_splits(kind, M, N);
 }
 

@@ -138,6 +138,27 @@ int dicp_lddmm_ode_ext_fwd_f32(const float* x, int64_t N, const float* q, const 
                                int64_t M, int D, double sigma, double eta, float* vx, float* gx,
                                void* ws, size_t ws_bytes, dicp_stream_t stream);
 
+/* Velocity gradient at the carried points (no reference counterpart): next to vx_i = v(x_i),
+ * the D x D matrix A_i[d][a] = dv_d/dx_a (x_i), row-major (N, D, D).  With s = 1/sigma^2,
+ * z = x_i - q_j, K = exp(-s |z|^2 / 2):
+ *   A_i[d][a] = -s sum_j K z_a p_j[d] + eta s (delta_da sum_j K - s sum_j K z_d z_a),
+ * whose trace is -gx_i of dicp_lddmm_ode_ext_fwd_f32.  vx may be NULL.  D = 2 or 3 (otherwise
+ * DICP_ERR_UNSUPPORTED).  N = 0 or M = 0 launch no kernel (M = 0: vx and A are zeroed).
+ * Deterministic (no atomics).  Workspace kind DICP_WS_ODE_EXT_JAC. */
+int dicp_lddmm_ode_ext_jac_f32(const float* x, int64_t N, const float* q, const float* p,
+                               int64_t M, int D, double sigma, double eta, float* vx, float* A,
+                               void* ws, size_t ws_bytes, dicp_stream_t stream);
+
+/* One Euler step of the carried points and of the displacement gradient G = J - I of their
+ * discrete flow (J = d x_t / d x_0), in one pass:
+ *   x_next = x + dt v(x),   G_next = G + dt A (I + G)      (A as above, at (x; q, p)).
+ * G (N, D, D) may be NULL = zero (the first step).  Outputs must not alias inputs.  M = 0:
+ * x_next = x, G_next = G.  Workspace kind DICP_WS_ODE_EXT_JAC. */
+int dicp_lddmm_ext_jac_step_f32(const float* x, const float* G, int64_t N, const float* q,
+                                const float* p, int64_t M, int D, double sigma, double eta,
+                                double dt, float* x_next, float* G_next, void* ws,
+                                size_t ws_bytes, dicp_stream_t stream);
+
 /* VJP of the external-point terms.  Cotangents gvx (N,D) on vx and device scalar gdiv on
  * sum_i gx_i.  Writes gxo (N,D) (gradient w.r.t. x) and ACCUMULATES into gq, gp (M,D)
  * (gradient w.r.t. the support points / momenta), so it can follow the self backward. */
@@ -415,7 +436,9 @@ enum dicp_ws_kind {
   DICP_WS_ODE_SELF_BWD_PART = 10, /* M = points, N = nparts */
   DICP_WS_GRAD = 11,             /* dicp_gauss_red_grad_f32: M rows, N columns */
   DICP_WS_ODE_SELF_FWD_PHASED = 12, /* dicp_lddmm_euler_step_phase_f32: M = rows, N = points */
-  DICP_WS_GMM_ASSIGN = 13        /* dicp_gmm_assign_f32: M = rows, N = columns */
+  DICP_WS_GMM_ASSIGN = 13,       /* dicp_gmm_assign_f32: M = rows, N = columns */
+  DICP_WS_ODE_EXT_JAC = 14       /* dicp_lddmm_ode_ext_jac_f32 / dicp_lddmm_ext_jac_step_f32: M = support
+                                    points, N = carried points (as DICP_WS_ODE_EXT_FWD) */
 };
 size_t dicp_workspace_bytes(int kind, int64_t M, int64_t N, int D);
 
