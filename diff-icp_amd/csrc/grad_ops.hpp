@@ -3,8 +3,10 @@
 // reference differentiates them through KeOps' / torch's autodiff (kernel.py:147-168,
 // :194-207, :284-292); here each gradient is one more row reduction of the same tiled
 // skeleton (common.hpp rowred_kernel), with the pair formula derived by hand
-// ("Gradients of the reductions"; checked against float64 autograd of
-// the oracle in tests/test_gpu_kernel_grads.py).
+// ("gradients of every reduction").  tests/test_gpu_kernel_grads.py
+// compares every kind and operand pattern with the float64 statement of the formulas below
+// (tests/fake_hip.py) at one-row, one-column, multi-block and multi-chunk shapes;
+// tests/test_host_logic.py pins that statement against float64 autograd of the oracle.
 //
 // One generic record layout: rows carry x_i and two optional D-vectors R1_i, R2_i; columns
 // carry y_j, two optional D-vectors C1_j, C2_j and an optional scalar cw_j.  A NULL pointer

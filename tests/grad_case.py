@@ -1,7 +1,14 @@
 """Shared body of the reduction-gradient tests (CPU spec: tests/test_host_logic.py; GPU:
 tests/test_gpu_model.py): autograd through GaussKernel's GenDKRed, HessKRed, GradLapKRed,
 DDKRed and GradKRed_rev (kernel.py:147-168, :194-207, :284-292) against float64 torch
-autograd through the oracle, w.r.t. every input."""
+autograd through the oracle, w.r.t. every input.
+
+This goes through the autograd classes of tools/kernel.py at one shape (one column chunk, one
+row block) and sees each gradient as a sum of terms.  The entry points underneath are
+compared one by one with float64 -- every kind and operand pattern of dicp_gauss_red_grad_f32,
+GRADKSCAL and GRADLAPKSCAL, at split, multi-block and one-row / one-column shapes -- in
+tests/test_gpu_kernel_grads.py (inputs: tests/kernel_grads_case.py; that those inputs can
+expose a wrong term: tests/test_kernel_grads_host.py)."""
 import torch
 
 from conftest import rel_err
