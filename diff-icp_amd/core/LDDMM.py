@@ -474,7 +474,8 @@ class LDDMMModel:
         if (last is not None and last[0]() is q0 and last[1] == q0._version
                 and last[2] == float(self.Kernel.sigma)):
             return last[3] > self.RAW_EXTENT_SIGMA
-        ext = float((q0.amax(0) - q0.amin(0)).norm()) / float(self.Kernel.sigma)
+        qd = q0.detach()      # q0 may require a gradient (float() of such a tensor warns)
+        ext = float((qd.amax(0) - qd.amin(0)).norm()) / float(self.Kernel.sigma)
         _EXTENT_MEMO.last = (weakref.ref(q0), q0._version, float(self.Kernel.sigma), ext)
         return ext > self.RAW_EXTENT_SIGMA
 

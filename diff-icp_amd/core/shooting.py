@@ -725,6 +725,13 @@ class ShootFn(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, gQ, gP, gC, *rest):
+        """The discrete adjoint for cotangents on every state (gQ, gP, gC[, gX]: stacked over t, or
+        None) and on H0, by one of the routes: cutoff (_cut_backward), captured graph
+        (_graph_backward), row split, fused Euler (euler_adjoint_step), general (_vjp).  Every
+        route but the row split is compared with float64 autograd of the oracle for every
+        cotangent pattern and every input in tests/test_gpu_shoot_adjoint.py (device) and
+        tests/test_shoot_adjoint_host.py (host logic on the float64 spec kernels); the row split in
+        tests/test_rowsplit_gloo.py and tests/test_gpu_rowsplit.py."""
         gX, gH = rest if len(rest) == 2 else (None, rest[0])
         sigma, eta, nt, scheme, want_div, has_x = \
             ctx.sigma, ctx.eta, ctx.nt, ctx.scheme, ctx.want_div, ctx.has_x
