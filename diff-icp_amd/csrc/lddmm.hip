@@ -10,7 +10,10 @@
 
 #include <stdlib.h>
 
+#include <algorithm>
 #include <cmath>
+#include <initializer_list>
+#include <type_traits>
 
 using namespace dicp;
 
@@ -70,35 +73,59 @@ struct MfmaRmaxInit {
   MfmaRmaxInit() { if (mfma_rmax_x100() < 0) mfma_rmax_x100() = DICP_MFMA_RMAX_X100; }
 } g_mfma_rmax_init;
 
+// Run-time values to template arguments.  A functor receives the value as an integral constant
+// (`decltype(d)::value`) or the operator as a tag (`op_of<decltype(t)>`).
+template <int V> using Int = std::integral_constant<int, V>;
+template <class Op> struct OpTag { using type = Op; };
+template <class Tag> using op_of = typename Tag::type;
+template <size_t N> size_t max_of(const size_t (&v)[N]) { return *std::max_element(v, v + N); }
+
+bool supported_dim(int D) { return D == 2 || D == 3; }
+
+// f(Int<D>) for a supported D ...
+template <class F>
+auto for_dim(int D, F&& f) {
+  return D == 2 ? f(Int<2>{}) : f(Int<3>{});
+}
+// ... and for the D of an entry point, which may be any
+template <class F>
+int with_dim(int D, const char* entry, F&& f) {
+  if (!supported_dim(D)) {
+    set_error("%s: D=%d unsupported (compiled in: 2, 3)", entry, D);
+    return DICP_ERR_UNSUPPORTED;
+  }
+  return for_dim(D, f);
+}
+
+// f(Int<R>) for the rows per thread of an ordered scalar pass (r_fwd() / r_bwd(): 1, 2 or 4)
+template <class F>
+auto for_rows(int R, F&& f) {
+  return R == 1 ? f(Int<1>{}) : R == 4 ? f(Int<4>{}) : f(Int<2>{});
+}
+
+// f(std::bool_constant<b>)
+template <class F>
+auto for_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
 template <class Op>
 int launch_r(int R, const char* name, const Args& a, const Scal& sc, int64_t M, int64_t N,
              const Outs& o, void* ws, size_t wsb, hipStream_t st) {
-  switch (R) {
-    case 1: return launch_rowred<Op, 1>(name, a, sc, M, N, o, ws, wsb, st);
-    case 4: return launch_rowred<Op, 4>(name, a, sc, M, N, o, ws, wsb, st);
-    default: return launch_rowred<Op, 2>(name, a, sc, M, N, o, ws, wsb, st);
-  }
+  return for_rows(R, [&](auto r) { return launch_rowred<Op, decltype(r)::value>(name, a, sc, M, N, o, ws, wsb, st); });
 }
 
 template <class Op>
 size_t ws_r(int R, int64_t M, int64_t N) {
-  switch (R) {
-    case 1: return rowred_ws_bytes<Op, 1>(M, N);
-    case 4: return rowred_ws_bytes<Op, 4>(M, N);
-    default: return rowred_ws_bytes<Op, 2>(M, N);
-  }
+  return for_rows(R, [&](auto r) { return rowred_ws_bytes<Op, decltype(r)::value>(M, N); });
 }
 
 template <template <int> class OpT>
 int red_dispatch(const char* name, int D, const Args& a, const Scal& sc, int64_t M, int64_t N,
                  float* out, void* ws, size_t wsb, hipStream_t st) {
-  const Outs o = make_outs(out);
-  switch (D) {
-    case 2: return launch_rowred<OpT<2>, kR>(name, a, sc, M, N, o, ws, wsb, st);
-    case 3: return launch_rowred<OpT<3>, kR>(name, a, sc, M, N, o, ws, wsb, st);
-    default: set_error("%s: D=%d not compiled in (supported: 2, 3)", name, D);
-      return DICP_ERR_UNSUPPORTED;
-  }
+  return with_dim(D, name, [&](auto d) {
+    return launch_rowred<OpT<decltype(d)::value>, kR>(name, a, sc, M, N, make_outs(out), ws, wsb, st);
+  });
 }
 
 template <int D> using OpGradLapKPlain = OpGradLapK<D, false>;
@@ -106,10 +133,8 @@ template <int D> using OpGradLapKScal = OpGradLapK<D, true>;
 
 template <template <int> class OpT>
 size_t red_ws(int D, int64_t M, int64_t N) {
-  return D == 2 ? rowred_ws_bytes<OpT<2>, kR>(M, N) : rowred_ws_bytes<OpT<3>, kR>(M, N);
+  return for_dim(D, [&](auto d) { return rowred_ws_bytes<OpT<decltype(d)::value>, kR>(M, N); });
 }
-
-bool supported_dim(int D) { return D == 2 || D == 3; }
 
 // Scaled-coordinate ops (OpOdeSelfFwd / OpOdeSelfBwd): alpha = sqrt(log2 e / (2 sigma^2)),
 // aux1 = s / alpha.
@@ -129,147 +154,139 @@ void raw_coords(Args& a, Scal& sc) {
   sc.aux1 = sc.s;
 }
 
-template <class OpS, class OpR>
-int launch_fwd_pk(bool raw, const char* name, Args a, Scal sc, int64_t nrows, int64_t M, const Outs& o,
-                  void* ws, size_t wsb, hipStream_t st) {
-  if (raw) {
-    raw_coords(a, sc);
-    return launch_rowred_pk<OpR>(name, a, sc, nrows, M, o, ws, wsb, st);
-  }
-  return launch_rowred_pk<OpS>(name, a, sc, nrows, M, o, ws, wsb, st);
+// ---- the packed ordered forward (packed.hpp OpOdeSelfFwdPk): THE variant table ----
+// One pass: the divergence sums (g rows), the eta terms, the Gs' sums (mG), the divergence rows
+// (zs) and original-unit coordinates.  Everything that launches or sizes these passes goes
+// through visit_pk_fwd / for_each_pk_fwd, so a new variant is added here and nowhere else.
+struct PkFwd {
+  bool div, eta, g, zs, raw;
+};
+// the variants that exist (the static_assert of the operator: zs rows have the divergence sums
+// and no eta; the eta sums contain the divergence's, so eta comes with div only)
+constexpr bool pk_fwd_exists(PkFwd v) { return (!v.zs || (v.div && !v.eta)) && (!v.eta || v.div); }
+
+template <int D, bool DIV, bool ETA, bool G, bool ZS, class F>
+auto pk_fwd_coords(bool raw, F&& f) {
+  return raw ? f(OpTag<OpOdeSelfFwdPk<D, DIV, ETA, G, ZS, true>>{})
+             : f(OpTag<OpOdeSelfFwdPk<D, DIV, ETA, G, ZS, false>>{});
 }
-template <class OpS, class OpR>
+// f(OpTag<the pass>) for the flags; zs and eta imply div
+template <int D, class F>
+auto visit_pk_fwd(PkFwd v, F&& f) {
+  if (v.zs)
+    return v.g ? pk_fwd_coords<D, true, false, true, true>(v.raw, f)
+               : pk_fwd_coords<D, true, false, false, true>(v.raw, f);
+  if (v.eta)
+    return v.g ? pk_fwd_coords<D, true, true, true, false>(v.raw, f)
+               : pk_fwd_coords<D, true, true, false, false>(v.raw, f);
+  if (v.div)
+    return v.g ? pk_fwd_coords<D, true, false, true, false>(v.raw, f)
+               : pk_fwd_coords<D, true, false, false, false>(v.raw, f);
+  return v.g ? pk_fwd_coords<D, false, false, true, false>(v.raw, f)
+             : pk_fwd_coords<D, false, false, false, false>(v.raw, f);
+}
+// f(OpTag<pass>) for every variant that exists
+template <int D, class F>
+void for_each_pk_fwd(F&& f) {
+  for (int i = 0; i < 32; ++i) {
+    const PkFwd v = {(i & 1) != 0, (i & 2) != 0, (i & 4) != 0, (i & 8) != 0, (i & 16) != 0};
+    if (pk_fwd_exists(v)) visit_pk_fwd<D>(v, f);
+  }
+}
+
+const char* pk_fwd_name(PkFwd v) {
+  if (v.zs) return v.g ? "ode_self_fwd(pk, zs)" : "ode_self_fwd(pk, no mG, zs)";
+  if (v.eta) return v.g ? "ode_self_fwd_eta(pk)" : "ode_self_fwd_eta(pk, no mG)";
+  return v.g ? "ode_self_fwd(pk)" : "ode_self_fwd(pk, no mG)";
+}
+
+template <int D>
+int launch_fwd_pk(PkFwd v, Args a, Scal sc, int64_t nrows, int64_t M, const Outs& o, void* ws, size_t wsb,
+                  hipStream_t st) {
+  if (v.raw) raw_coords(a, sc);
+  return visit_pk_fwd<D>(v, [&](auto t) {
+    return launch_rowred_pk<op_of<decltype(t)>>(pk_fwd_name(v), a, sc, nrows, M, o, ws, wsb, st);
+  });
+}
+template <int D>
 size_t fwd_pk_ws(int64_t nrows, int64_t M) {
-  const size_t a = rowred_pk_ws_bytes<OpS>(nrows, M), b = rowred_pk_ws_bytes<OpR>(nrows, M);
-  return a > b ? a : b;
+  size_t m = 0;
+  for_each_pk_fwd<D>([&](auto t) { m = std::max(m, rowred_pk_ws_bytes<op_of<decltype(t)>>(nrows, M)); });
+  return m;
 }
 
 }  // namespace
 
 extern "C" int dicp_supports_dim(int D) { return supported_dim(D) ? 1 : 0; }
 
-// Tuning knobs (A/B measurements in one process): "r_fwd", "r_bwd" in {1, 2, 4}.
+// Tuning knobs (include/difficp_hip.h lists them in this order): one row per option, read by
+// dicp_set_option and dicp_get_option alike.
+namespace {
+struct Option {
+  const char* name;
+  int (*get)();
+  void (*set)(int);
+  int lo, hi;        // allowed range ...
+  const int* only;   // ... or, when not NULL, the allowed set (ends with -1)
+  bool or_zero;      // 0 (automatic) is allowed besides the range
+  bool per_thread;   // the value belongs to the calling host thread
+};
+#define DICP_OPTION(name, read, lvalue, ...) \
+  {name, [] { return (int)(read); }, [](int v) { lvalue = v; }, __VA_ARGS__}
+constexpr int kNoMax = INT32_MAX;
+constexpr int kRows124[] = {1, 2, 4, -1}, kRows0468[] = {0, 4, 6, 8, -1}, kRows048[] = {0, 4, 8, -1};
+const Option kOptions[] = {
+    DICP_OPTION("fwd_alg", g_fwd_alg, g_fwd_alg, 0, 6),
+    DICP_OPTION("bwd_alg", g_bwd_alg, g_bwd_alg, 0, 3),
+    DICP_OPTION("bwd_eta_alg", g_bwd_eta_alg, g_bwd_eta_alg, 0, 2),
+    DICP_OPTION("r_fwd", r_fwd(), g_r_fwd, 0, 0, kRows124),
+    DICP_OPTION("r_bwd", r_bwd(), g_r_bwd, 0, 0, kRows124),
+    DICP_OPTION("split_rounds", split_rounds(), split_rounds(), 0, 64),
+    DICP_OPTION("force_splits", force_splits(), force_splits(), 0, 65536),
+    DICP_OPTION("sym_L", sym_L(), sym_L(), 0, 64),
+    DICP_OPTION("min_chunk", min_chunk(), min_chunk(), 16, 65536, nullptr, true),
+    DICP_OPTION("pk_rp", pk_rp_force(), pk_rp_force(), 0, kPkRPMax),
+    DICP_OPTION("sym_rp", sym_rp(), sym_rp(), 0, 2),
+    DICP_OPTION("red_alg", red_alg(), red_alg(), 0, 2),
+    DICP_OPTION("sym_red", sym_red(), sym_red(), 0, 2),
+    DICP_OPTION("sym_red_rows", sym_red_rows(), sym_red_rows(), 0, 0, kRows048),
+    DICP_OPTION("sym_fwd_rows", sym_fwd_rows(), sym_fwd_rows(), 0, 0, kRows0468),
+    DICP_OPTION("pair_cutoff", pair_cutoff(), pair_cutoff(), 0, 2),
+    DICP_OPTION("pair_cutoff_log2", pair_cutoff_log2(), pair_cutoff_log2(), 8, 150),
+    DICP_OPTION("lse_pk", lse_pk(), lse_pk(), 0, 1),
+    DICP_OPTION("lse_adapt", lse_adapt(), lse_adapt(), 0, kNoMax),
+    DICP_OPTION("lse_bound", lse_bound(), lse_bound(), 0, 1),
+    DICP_OPTION("cx_rho_x100", cx_rho_x100(), cx_rho_x100(), 0, 100000),
+    DICP_OPTION("mfma_rmax_x100", mfma_rmax_x100(), mfma_rmax_x100(), 0, kNoMax),
+    DICP_OPTION("ext_alg", g_ext_alg, g_ext_alg, 0, 1),
+    DICP_OPTION("batch_share", batch_share(), tl_batch_share, 1, 4096, nullptr, false, true),
+    DICP_OPTION("coord_raw", tl_coord_raw, tl_coord_raw, 0, 1, nullptr, false, true),
+};
+#undef DICP_OPTION
+
+const Option* find_option(const char* name) {
+  for (const Option& o : kOptions)
+    if (!strcmp(name, o.name)) return &o;
+  return nullptr;
+}
+bool option_allows(const Option& o, int v) {
+  if (v == 0 && o.or_zero) return true;
+  if (o.only == nullptr) return v >= o.lo && v <= o.hi;
+  for (const int* s = o.only; *s >= 0; ++s)
+    if (*s == v) return true;
+  return false;
+}
+}  // namespace
+
 extern "C" int dicp_set_option(const char* name, int value) {
-  if (!strcmp(name, "split_rounds")) {
-    if (value < 0 || value > 64) return DICP_ERR_INVALID;  // 0 = automatic
-    split_rounds() = value;
-    return DICP_OK;
+  const Option* o = name ? find_option(name) : nullptr;
+  if (o == nullptr) {
+    set_error("dicp_set_option: unknown option %s", name ? name : "(NULL)");
+    return DICP_ERR_INVALID;
   }
-  if (!strcmp(name, "sym_L")) {
-    if (value < 0 || value > 64) return DICP_ERR_INVALID;  // 0 = automatic
-    sym_L() = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "min_chunk")) {
-    if (value != 0 && (value < 16 || value > 65536)) return DICP_ERR_INVALID;   // 0 = automatic
-    min_chunk() = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "force_splits")) {
-    if (value < 0 || value > 65536) return DICP_ERR_INVALID;
-    force_splits() = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "batch_share")) {   // PER HOST THREAD geometry hint (batch.hpp)
-    if (value < 1 || value > 4096) return DICP_ERR_INVALID;
-    tl_batch_share = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "sym_rp")) {   // packed eta = 0 VJP: row pairs per lane (1, 2), 0 = automatic
-    if (value < 0 || value > 2) return DICP_ERR_INVALID;
-    sym_rp() = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "pk_rp")) {   // packed row passes: row pairs per thread, 0 = automatic
-    if (value < 0 || value > kPkRPMax) return DICP_ERR_INVALID;
-    pk_rp_force() = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "fwd_alg")) {
-    if (value < 0 || value > 6) return DICP_ERR_INVALID;
-    g_fwd_alg = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "mfma_rmax_x100")) {  // >= 100000: always the MFMA branch, 0: never
-    if (value < 0) return DICP_ERR_INVALID;
-    mfma_rmax_x100() = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "bwd_eta_alg")) {
-    if (value < 0 || value > 2) return DICP_ERR_INVALID;
-    g_bwd_eta_alg = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "bwd_alg")) {
-    if (value < 0 || value > 3) return DICP_ERR_INVALID;
-    g_bwd_alg = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "red_alg")) {
-    if (value < 0 || value > 2) return DICP_ERR_INVALID;
-    red_alg() = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "coord_raw")) {
-    if (value < 0 || value > 1) return DICP_ERR_INVALID;
-    tl_coord_raw = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "ext_alg")) {
-    if (value < 0 || value > 1) return DICP_ERR_INVALID;
-    g_ext_alg = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "cx_rho_x100")) {
-    if (value < 0 || value > 100000) return DICP_ERR_INVALID;
-    cx_rho_x100() = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "sym_fwd_rows")) {
-    if (value != 0 && value != 4 && value != 6 && value != 8) return DICP_ERR_INVALID;
-    sym_fwd_rows() = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "sym_red")) {
-    if (value < 0 || value > 2) return DICP_ERR_INVALID;
-    sym_red() = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "lse_adapt")) {
-    if (value < 0) return DICP_ERR_INVALID;
-    lse_adapt() = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "lse_bound")) {
-    if (value < 0 || value > 1) return DICP_ERR_INVALID;
-    lse_bound() = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "lse_pk")) {
-    if (value < 0 || value > 1) return DICP_ERR_INVALID;
-    lse_pk() = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "sym_red_rows")) {
-    if (value != 0 && value != 4 && value != 8) return DICP_ERR_INVALID;
-    sym_red_rows() = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "pair_cutoff")) {   // Gaussian cutoff of far tile pairs: 0 off, 1 automatic, 2 always
-    if (value < 0 || value > 2) return DICP_ERR_INVALID;
-    pair_cutoff() = value;
-    return DICP_OK;
-  }
-  if (!strcmp(name, "pair_cutoff_log2")) {   // T: a skipped pair has K < 2^-T (kPairCutoffLog2)
-    if (value < 8 || value > 150) return DICP_ERR_INVALID;
-    pair_cutoff_log2() = value;
-    return DICP_OK;
-  }
-  if (value != 1 && value != 2 && value != 4) return DICP_ERR_INVALID;
-  if (!strcmp(name, "r_fwd")) { g_r_fwd = value; return DICP_OK; }
-  if (!strcmp(name, "r_bwd")) { g_r_bwd = value; return DICP_OK; }
-  set_error("dicp_set_option: unknown option %s", name);
-  return DICP_ERR_INVALID;
+  if (!option_allows(*o, value)) return DICP_ERR_INVALID;
+  o->set(value);
+  return DICP_OK;
 }
 
 extern "C" int dicp_get_option(const char* name, int* value) {
@@ -277,33 +294,13 @@ extern "C" int dicp_get_option(const char* name, int* value) {
     set_error("dicp_get_option: NULL argument");
     return DICP_ERR_INVALID;
   }
-  if (!strcmp(name, "split_rounds")) { *value = split_rounds(); return DICP_OK; }
-  if (!strcmp(name, "sym_L")) { *value = sym_L(); return DICP_OK; }
-  if (!strcmp(name, "force_splits")) { *value = force_splits(); return DICP_OK; }
-  if (!strcmp(name, "min_chunk")) { *value = (int)min_chunk(); return DICP_OK; }
-  if (!strcmp(name, "pk_rp")) { *value = pk_rp_force(); return DICP_OK; }
-  if (!strcmp(name, "sym_rp")) { *value = sym_rp(); return DICP_OK; }
-  if (!strcmp(name, "batch_share")) { *value = batch_share(); return DICP_OK; }
-  if (!strcmp(name, "fwd_alg")) { *value = g_fwd_alg; return DICP_OK; }
-  if (!strcmp(name, "mfma_rmax_x100")) { *value = mfma_rmax_x100(); return DICP_OK; }
-  if (!strcmp(name, "bwd_eta_alg")) { *value = g_bwd_eta_alg; return DICP_OK; }
-  if (!strcmp(name, "bwd_alg")) { *value = g_bwd_alg; return DICP_OK; }
-  if (!strcmp(name, "red_alg")) { *value = red_alg(); return DICP_OK; }
-  if (!strcmp(name, "cx_rho_x100")) { *value = cx_rho_x100(); return DICP_OK; }
-  if (!strcmp(name, "sym_red")) { *value = sym_red(); return DICP_OK; }
-  if (!strcmp(name, "lse_pk")) { *value = lse_pk(); return DICP_OK; }
-  if (!strcmp(name, "lse_adapt")) { *value = lse_adapt(); return DICP_OK; }
-  if (!strcmp(name, "lse_bound")) { *value = lse_bound(); return DICP_OK; }
-  if (!strcmp(name, "sym_red_rows")) { *value = sym_red_rows(); return DICP_OK; }
-  if (!strcmp(name, "sym_fwd_rows")) { *value = sym_fwd_rows(); return DICP_OK; }
-  if (!strcmp(name, "ext_alg")) { *value = g_ext_alg; return DICP_OK; }
-  if (!strcmp(name, "coord_raw")) { *value = tl_coord_raw; return DICP_OK; }
-  if (!strcmp(name, "pair_cutoff")) { *value = pair_cutoff(); return DICP_OK; }
-  if (!strcmp(name, "pair_cutoff_log2")) { *value = pair_cutoff_log2(); return DICP_OK; }
-  if (!strcmp(name, "r_fwd")) { *value = r_fwd(); return DICP_OK; }
-  if (!strcmp(name, "r_bwd")) { *value = r_bwd(); return DICP_OK; }
-  set_error("dicp_get_option: unknown option %s", name);
-  return DICP_ERR_INVALID;
+  const Option* o = find_option(name);
+  if (o == nullptr) {
+    set_error("dicp_get_option: unknown option %s", name);
+    return DICP_ERR_INVALID;
+  }
+  *value = o->get();
+  return DICP_OK;
 }
 
 extern "C" int dicp_gauss_red_f32(int op, const float* x, int64_t M, const float* y, int64_t N,
@@ -380,7 +377,7 @@ namespace {
 // packed forward algorithms: 2 (default: ordered rows, the symmetric 4-row pass for whole
 // passes from DICP_SYM_FWD4_MIN_M points), 5 (symmetric 4-row wherever it applies), 6 (ordered
 // rows always)
-bool packed_fwd_alg() { return g_fwd_alg == 2 || g_fwd_alg == 5 || g_fwd_alg == 6; }
+bool packed_fwd_alg(int alg) { return alg == 2 || alg == 5 || alg == 6; }
 #ifndef DICP_SYM_FWD4_MIN_M
 #define DICP_SYM_FWD4_MIN_M 20000
 #endif
@@ -392,9 +389,9 @@ bool packed_fwd_alg() { return g_fwd_alg == 2 || g_fwd_alg == 5 || g_fwd_alg == 
 // below 75k: r04_ab_fwd_sym4.jsonl) -- from 20k points, or, with the geometry hint
 // batch_share > 1 (concurrent / batched frames), when the sharing calls have >= 1e9 pairs
 // (as the 4-row VJP, lddmm_sym.hpp DICP_SYM_SHARE4_MIN_PAIRS).
-bool use_sym_fwd4(int64_t M, bool all, bool raw) {
-  if (!all || raw || g_fwd_alg == 6 || !(g_fwd_alg == 2 || g_fwd_alg == 5)) return false;
-  if (g_fwd_alg == 5) return true;
+bool use_sym_fwd4(int alg, int64_t M, bool all, bool raw) {
+  if (!all || raw || !(alg == 2 || alg == 5)) return false;
+  if (alg == 5) return true;
   if (batch_share() > 1) return M >= 8192 && (double)M * (double)M * batch_share() >= DICP_SYM_SHARE4_MIN_PAIRS;
   return M >= DICP_SYM_FWD4_MIN_M;
 }
@@ -430,6 +427,27 @@ int launch_sym_fwd_rows(const Args& a, const Scal& sc, int64_t M, const Outs& o,
   }
 }
 
+// Which kernel family runs a forward pass: the one rule, first match wins.
+enum class FwdFamily { kPacked, kScalar, kSym, kMfma, kSymRows, kZsUnsupported };
+struct FwdWant {   // the pass's terms and outputs
+  bool eta, mg, div, h, zs;
+};
+FwdFamily fwd_family(int alg, bool all, bool raw, FwdWant w, int64_t M) {
+  if (w.zs) {
+    // divergence rows out through the (unused) h slot: the packed passes only
+    if (w.eta || w.h || (w.mg && !packed_fwd_alg(alg))) return FwdFamily::kZsUnsupported;
+    // (the mG-less last step keeps the ordered pass without the Gs' sums: 2.49 against 3.27 ms
+    // for the symmetric pass, which forms them anyway, at 100k)
+    return w.mg && use_sym_fwd4(alg, M, all, raw) ? FwdFamily::kSymRows : FwdFamily::kPacked;
+  }
+  if (w.eta) return alg >= 2 ? FwdFamily::kPacked : FwdFamily::kScalar;
+  if (!w.mg) return FwdFamily::kPacked;   // mG not wanted: the packed forward without the Gs' sums
+  if ((alg == 1 || alg == 4) && all) return FwdFamily::kSym;
+  if (alg == 3) return FwdFamily::kMfma;
+  if (use_sym_fwd4(alg, M, all, raw)) return FwdFamily::kSymRows;   // pair-once, 4 / 6 / 8 rows per lane
+  return alg >= 2 ? FwdFamily::kPacked : FwdFamily::kScalar;
+}
+
 // rows [row0, row0 + nrows) of the pass against all M columns (row-split over ranks);
 // nrows < 0: all rows.  Output pointers in `o` address the row slice.
 // order: optional nrows int32 row indices (a permutation of the slice's rows) that groups
@@ -437,224 +455,151 @@ int launch_sym_fwd_rows(const Args& a, const Scal& sc, int64_t M, const Outs& o,
 // fp32 error grows with the spread of a workgroup's rows (mfma_fwd.hpp); ignored otherwise.
 template <int D>
 int ode_self_fwd_d(const float* q, const float* p, int64_t M, double sigma, double eta,
-                   const Outs& o, void* ws, size_t wsb, hipStream_t st, int64_t row0 = 0,
+                   Outs o, void* ws, size_t wsb, hipStream_t st, int64_t row0 = 0,
                    int64_t nrows = -1, const int* order = nullptr, float* zs = nullptr) {
   if (nrows < 0) nrows = M;
   const bool all = row0 == 0 && nrows == M;
   Args a = {q + row0 * D, p + row0 * D, nullptr, nullptr, q, p, nullptr, nullptr, 0.f};
   Scal sc = make_scal(sigma, eta);
   scale_coords(a, sc, sigma);
-  const bool raw = tl_coord_raw != 0;   // the packed kernels below; the others stay scaled
-  if (zs != nullptr) {
-    // divergence rows out through the (unused) h slot: the packed passes only
-    if (eta != 0.0 || o.ptr[3] != nullptr || (o.ptr[1] != nullptr && !packed_fwd_alg())) {
-      set_error("ode_self_fwd: divergence rows (zs) need eta = 0, no h output and fwd_alg 2, 5 or 6");
-      return DICP_ERR_INVALID;
-    }
-    Outs oz = o;
-    oz.ptr[3] = zs;
-    oz.base[3] = oz.add[3] = nullptr;
-    oz.accumulate[3] = 0;
-    oz.alpha[3] = 1.f;
-    // (the mG-less last step keeps the ordered pass without the Gs' sums: 2.49 against 3.27 ms
-    // for the symmetric pass, which forms them anyway, at 100k)
-    if (o.ptr[1] != nullptr && use_sym_fwd4(M, all, raw))
-      return launch_sym_fwd_rows<D, true>(a, sc, M, oz, ws, wsb, st, true);
-    if (o.ptr[1] == nullptr)
-      return launch_fwd_pk<OpOdeSelfFwdPk<D, true, false, false, true>, OpOdeSelfFwdPk<D, true, false, false, true, true>>(raw, "ode_self_fwd(pk, no mG, zs)", a, sc, nrows,
-                                                                           M, oz, ws, wsb, st);
-    return launch_fwd_pk<OpOdeSelfFwdPk<D, true, false, true, true>, OpOdeSelfFwdPk<D, true, false, true, true, true>>(raw, "ode_self_fwd(pk, zs)", a, sc, nrows, M, oz,
-                                                                        ws, wsb, st);
+  const bool raw = tl_coord_raw != 0;   // the packed kernels; the others stay scaled
+  const FwdWant w = {eta != 0.0, o.ptr[1] != nullptr, o.ptr[2] != nullptr || zs != nullptr,
+                     o.ptr[3] != nullptr, zs != nullptr};
+  const FwdFamily fam = fwd_family(g_fwd_alg, all, raw, w, M);
+  if (fam == FwdFamily::kZsUnsupported) {
+    set_error("ode_self_fwd: divergence rows (zs) need eta = 0, no h output and fwd_alg 2, 5 or 6");
+    return DICP_ERR_INVALID;
   }
-  if (eta != 0.0) {
-    if (g_fwd_alg >= 2 && o.ptr[1] == nullptr)  // mG not wanted: without the Gs', Hs, GL' sums
-      return launch_fwd_pk<OpOdeSelfFwdPk<D, true, true, false>, OpOdeSelfFwdPk<D, true, true, false, false, true>>(raw, "ode_self_fwd_eta(pk, no mG)", a, sc, nrows, M, o,
-                                                                     ws, wsb, st);
-    return g_fwd_alg >= 2
-               ? launch_fwd_pk<OpOdeSelfFwdPk<D, true, true>, OpOdeSelfFwdPk<D, true, true, true, false, true>>(raw, "ode_self_fwd_eta(pk)", a, sc, nrows, M, o, ws, wsb, st)
-               : launch_r<OpOdeSelfFwd<D, true, true>>(r_fwd(), "ode_self_fwd", a, sc, nrows, M, o, ws, wsb, st);
+  if (w.zs) {
+    o.ptr[3] = zs;
+    o.base[3] = o.add[3] = nullptr;
+    o.accumulate[3] = 0;
+    o.alpha[3] = 1.f;
   }
-  if (o.ptr[1] == nullptr)  // mG not wanted (eta = 0): the packed forward without the Gs' sums
-    return o.ptr[2] != nullptr
-               ? launch_fwd_pk<OpOdeSelfFwdPk<D, true, false, false>, OpOdeSelfFwdPk<D, true, false, false, false, true>>(raw, "ode_self_fwd(pk, no mG)", a, sc, nrows, M, o, ws, wsb, st)
-               : launch_fwd_pk<OpOdeSelfFwdPk<D, false, false, false>, OpOdeSelfFwdPk<D, false, false, false, false, true>>(raw, "ode_self_fwd(pk, no mG)", a, sc, nrows, M, o, ws, wsb, st);
-  if ((g_fwd_alg == 1 || g_fwd_alg == 4) && all)
-    return o.ptr[2] != nullptr ? launch_sym_fwd<D, true>(a, sc, M, o, ws, wsb, st, g_fwd_alg == 4)
-                               : launch_sym_fwd<D, false>(a, sc, M, o, ws, wsb, st, g_fwd_alg == 4);
-  if (g_fwd_alg == 3)
-    return o.ptr[2] != nullptr
-               ? launch_mfma_fwd<D, true>("ode_self_fwd(mfma)", a, sc, nrows, M, o, ws, wsb, st, order)
-               : launch_mfma_fwd<D, false>("ode_self_fwd(mfma)", a, sc, nrows, M, o, ws, wsb, st, order);
-  if (use_sym_fwd4(M, all, raw)) {  // symmetric pair-once, 4 (or 8) rows per lane
-    return o.ptr[2] != nullptr ? launch_sym_fwd_rows<D, true>(a, sc, M, o, ws, wsb, st, false)
-                               : launch_sym_fwd_rows<D, false>(a, sc, M, o, ws, wsb, st, false);
+  switch (fam) {
+    case FwdFamily::kPacked:
+      return launch_fwd_pk<D>({w.div, w.eta, w.mg, w.zs, raw}, a, sc, nrows, M, o, ws, wsb, st);
+    case FwdFamily::kSym:
+      return for_bool(w.div, [&](auto div) {
+        return launch_sym_fwd<D, decltype(div)::value>(a, sc, M, o, ws, wsb, st, g_fwd_alg == 4);
+      });
+    case FwdFamily::kMfma:
+      return for_bool(w.div, [&](auto div) {
+        return launch_mfma_fwd<D, decltype(div)::value>("ode_self_fwd(mfma)", a, sc, nrows, M, o, ws, wsb, st, order);
+      });
+    case FwdFamily::kSymRows:
+      return for_bool(w.div, [&](auto div) {
+        return launch_sym_fwd_rows<D, decltype(div)::value>(a, sc, M, o, ws, wsb, st, w.zs);
+      });
+    default:   // kScalar (the eta sums contain the divergence's)
+      if (w.eta) return launch_r<OpOdeSelfFwd<D, true, true>>(r_fwd(), "ode_self_fwd", a, sc, nrows, M, o, ws, wsb, st);
+      return for_bool(w.div, [&](auto div) {
+        return launch_r<OpOdeSelfFwd<D, false, decltype(div)::value>>(r_fwd(), "ode_self_fwd", a, sc, nrows, M, o, ws, wsb, st);
+      });
   }
-  if (g_fwd_alg == 2 || g_fwd_alg == 4 || g_fwd_alg == 5 || g_fwd_alg == 6)
-    return o.ptr[2] != nullptr
-               ? launch_fwd_pk<OpOdeSelfFwdPk<D, true>, OpOdeSelfFwdPk<D, true, false, true, false, true>>(raw, "ode_self_fwd(pk)", a, sc, nrows, M, o, ws, wsb, st)
-               : launch_fwd_pk<OpOdeSelfFwdPk<D, false>, OpOdeSelfFwdPk<D, false, false, true, false, true>>(raw, "ode_self_fwd(pk)", a, sc, nrows, M, o, ws, wsb, st);
-  if (o.ptr[2] != nullptr)
-    return launch_r<OpOdeSelfFwd<D, false, true>>(r_fwd(), "ode_self_fwd", a, sc, nrows, M, o, ws, wsb, st);
-  return launch_r<OpOdeSelfFwd<D, false, false>>(r_fwd(), "ode_self_fwd", a, sc, nrows, M, o, ws, wsb, st);
 }
 
+// the workspace of every variant that ode_self_fwd_d may launch for nrows rows of M (their
+// occupancies, hence splits, differ); a whole pass may run a symmetric forward
 template <int D>
 size_t ode_self_fwd_rows_ws(int64_t nrows, int64_t M) {
-  size_t m = 0;
-  for (size_t v : {ws_r<OpOdeSelfFwd<D, true, true>>(r_fwd(), nrows, M),
-                   ws_r<OpOdeSelfFwd<D, false, true>>(r_fwd(), nrows, M),
-                   ws_r<OpOdeSelfFwd<D, false, false>>(r_fwd(), nrows, M),
-                   fwd_pk_ws<OpOdeSelfFwdPk<D, true>, OpOdeSelfFwdPk<D, true, false, true, false, true>>(nrows, M),
-                   fwd_pk_ws<OpOdeSelfFwdPk<D, false>, OpOdeSelfFwdPk<D, false, false, true, false, true>>(nrows, M),
-                   fwd_pk_ws<OpOdeSelfFwdPk<D, true, true>, OpOdeSelfFwdPk<D, true, true, true, false, true>>(nrows, M),
-                   fwd_pk_ws<OpOdeSelfFwdPk<D, true, false, false>, OpOdeSelfFwdPk<D, true, false, false, false, true>>(nrows, M),
-                   fwd_pk_ws<OpOdeSelfFwdPk<D, true, true, false>, OpOdeSelfFwdPk<D, true, true, false, false, true>>(nrows, M),
-                   fwd_pk_ws<OpOdeSelfFwdPk<D, false, false, false>, OpOdeSelfFwdPk<D, false, false, false, false, true>>(nrows, M),
-                   fwd_pk_ws<OpOdeSelfFwdPk<D, true, false, true, true>, OpOdeSelfFwdPk<D, true, false, true, true, true>>(nrows, M),
-                   fwd_pk_ws<OpOdeSelfFwdPk<D, true, false, false, true>, OpOdeSelfFwdPk<D, true, false, false, true, true>>(nrows, M),
-                   mfma_fwd_ws_bytes<D, true>(nrows, M), mfma_fwd_ws_bytes<D, false>(nrows, M)})
-    m = v > m ? v : m;
-  if (nrows == M) {   // a whole pass may run the symmetric 4-row forward (fwd_alg 5)
-    const size_t sy = sym_ws_bytes(M, 3 * D);
-    m = sy > m ? sy : m;
-  }
+  return max_of({ws_r<OpOdeSelfFwd<D, true, true>>(r_fwd(), nrows, M),
+                 ws_r<OpOdeSelfFwd<D, false, true>>(r_fwd(), nrows, M),
+                 ws_r<OpOdeSelfFwd<D, false, false>>(r_fwd(), nrows, M), fwd_pk_ws<D>(nrows, M),
+                 mfma_fwd_ws_bytes<D, true>(nrows, M), mfma_fwd_ws_bytes<D, false>(nrows, M),
+                 nrows == M ? sym_ws_bytes(M, 3 * D) : 0});
+}
+
+// ---- the ordered (row-reduction) VJP: eta != 0 its own operator, else bwd_alg 1 or 0 ----
+template <int D, class F>
+auto visit_bwd_ord(bool eta, int alg, F&& f) {
+  if (eta) return f(OpTag<OpOdeSelfBwdEta<D>>{});
+  return alg == 1 ? f(OpTag<OpOdeSelfBwd2<D>>{}) : f(OpTag<OpOdeSelfBwd<D>>{});
+}
+// workspace of any VJP kernel for part 1 / nparts of M points (nparts = 1: the whole VJP);
+// SymBwd and SymBwdEta: W = 2D
+template <int D>
+size_t ode_self_bwd_ws(int64_t M, int nparts) {
+  const int64_t per = (M + nparts - 1) / nparts;
+  size_t m = sym_ws_bytes(M, 2 * D, nparts);
+  for (int v = 0; v < 3; ++v)   // bwd_alg 0, bwd_alg 1, eta
+    visit_bwd_ord<D>(v == 2, v, [&](auto t) { m = std::max(m, ws_r<op_of<decltype(t)>>(r_bwd(), per, M)); });
   return m;
 }
 
-template <int D>
-size_t ode_self_fwd_ws(int64_t M) {
-  // every variant that ode_self_fwd_d may launch (their occupancies, hence splits, differ)
-  size_t a = ws_r<OpOdeSelfFwd<D, true, true>>(r_fwd(), M, M);
-  size_t b = ws_r<OpOdeSelfFwd<D, false, true>>(r_fwd(), M, M);
-  size_t c = ws_r<OpOdeSelfFwd<D, false, false>>(r_fwd(), M, M);
-  a = a > b ? a : b;
-  a = a > c ? a : c;
-  const size_t d = sym_ws_bytes(M, 3 * D);
-  a = a > d ? a : d;
-  for (size_t e : {fwd_pk_ws<OpOdeSelfFwdPk<D, true>, OpOdeSelfFwdPk<D, true, false, true, false, true>>(M, M),
-                   fwd_pk_ws<OpOdeSelfFwdPk<D, false>, OpOdeSelfFwdPk<D, false, false, true, false, true>>(M, M),
-                   fwd_pk_ws<OpOdeSelfFwdPk<D, true, true>, OpOdeSelfFwdPk<D, true, true, true, false, true>>(M, M),
-                   fwd_pk_ws<OpOdeSelfFwdPk<D, true, false, false>, OpOdeSelfFwdPk<D, true, false, false, false, true>>(M, M),
-                   fwd_pk_ws<OpOdeSelfFwdPk<D, true, true, false>, OpOdeSelfFwdPk<D, true, true, false, false, true>>(M, M),
-                   fwd_pk_ws<OpOdeSelfFwdPk<D, false, false, false>, OpOdeSelfFwdPk<D, false, false, false, false, true>>(M, M),
-                   fwd_pk_ws<OpOdeSelfFwdPk<D, true, false, true, true>, OpOdeSelfFwdPk<D, true, false, true, true, true>>(M, M),
-                   fwd_pk_ws<OpOdeSelfFwdPk<D, true, false, false, true>, OpOdeSelfFwdPk<D, true, false, false, true, true>>(M, M),
-                   mfma_fwd_ws_bytes<D, true>(M, M), mfma_fwd_ws_bytes<D, false>(M, M)})
-    a = a > e ? a : e;
-  return a;
-}
-
+// Pair subset `part` of `nparts` of the VJP (row-split over ranks; the sum over parts is the
+// full VJP; nparts = 1: the whole VJP, exactly the single-device kernel): symmetric kernels
+// (eta = 0, and eta != 0 packed) -> the quads Q = part (mod nparts), written to all rows;
+// otherwise (ordered kernels) the row slice [part * ceil(M/nparts), ...) against all columns,
+// other rows zero.  Outputs of a part are plain (no epilogue).
 template <int D>
 int ode_self_bwd_d(const float* q, const float* p, const float* gv, const float* gmG,
-                   const float* gdiv, int64_t M, double sigma, double eta, const Outs& o,
-                   void* ws, size_t wsb, hipStream_t st, const float* zs = nullptr, int64_t zr0 = 0,
-                   int64_t zn = 0) {
-  if (zs != nullptr && (eta != 0.0 || (gmG != nullptr && g_bwd_alg != 3))) {
-    set_error("ode_self_bwd: divergence rows (zs) need eta = 0 and the packed VJP (bwd_alg 3)");
-    return DICP_ERR_INVALID;
-  }
+                   const float* gdiv, int64_t M, double sigma, double eta, Outs o, void* ws,
+                   size_t wsb, hipStream_t st, const float* zs = nullptr, int64_t zr0 = 0,
+                   int64_t zn = 0, int part = 0, int nparts = 1) {
+  const char* who = nparts == 1 ? "ode_self_bwd" : "ode_self_bwd_part";
+  const bool has_eta = eta != 0.0;
   // gmG == NULL: zero cotangent on mG (the B0 symmetric packed kernels never read it; the
   // record slot is pointed at gv so every address stays valid)
   const bool b0 = gmG == nullptr;
-  if (b0 && eta != 0.0 && g_bwd_eta_alg != 2) {
-    set_error("ode_self_bwd: a NULL mG cotangent (zero) needs the packed eta kernel (bwd_eta_alg 2)");
+  const bool pk = b0 || g_bwd_alg == 3;   // eta = 0: the packed symmetric kernel
+  if (zs != nullptr && (has_eta || !pk)) {
+    set_error("%s: divergence rows (zs) need eta = 0 and the packed VJP (bwd_alg 3)", who);
+    return DICP_ERR_INVALID;
+  }
+  if (b0 && has_eta && g_bwd_eta_alg != 2) {
+    set_error("%s: a NULL mG cotangent (zero) needs the packed eta kernel (bwd_eta_alg 2)", who);
     return DICP_ERR_INVALID;
   }
   const float* gb = b0 ? gv : gmG;
   Args a = {q, p, gv, gb, q, p, gv, gb, 0.f};
-  if (eta != 0.0) {
-    Scal sc = make_scal(sigma, eta);
-    sc.dev0 = gdiv;
-    if (g_bwd_eta_alg >= 1)
-      return launch_sym_bwd_eta<D>(a, sc, M, o, ws, wsb, st, g_bwd_eta_alg == 2, 0, 1, b0);
-    return launch_r<OpOdeSelfBwdEta<D>>(r_bwd(), "ode_self_bwd_eta", a, sc, M, M, o, ws, wsb, st);
-  }
-  Scal sc = make_scal(sigma, 0.0);
-  scale_coords(a, sc, sigma);
+  Scal sc = make_scal(sigma, has_eta ? eta : 0.0);
   sc.dev0 = gdiv;  // nullptr -> aux0 = 0
-  const bool raw = tl_coord_raw != 0 && (b0 || g_bwd_alg == 3);   // packed kernels only
-  if (raw) raw_coords(a, sc);
-  if (b0) return launch_sym_bwd<D>(a, sc, M, o, ws, wsb, st, 0, 1, true, true, zs, zr0, zn, raw);
-  if (g_bwd_alg >= 2)
-    return launch_sym_bwd<D>(a, sc, M, o, ws, wsb, st, 0, 1, g_bwd_alg == 3, false, zs, zr0, zn, raw);
-  if (g_bwd_alg == 1)
-    return launch_r<OpOdeSelfBwd2<D>>(r_bwd(), "ode_self_bwd", a, sc, M, M, o, ws, wsb, st);
-  return launch_r<OpOdeSelfBwd<D>>(r_bwd(), "ode_self_bwd", a, sc, M, M, o, ws, wsb, st);
-}
-
-// Pair subset `part` of `nparts` of the VJP (row-split over ranks; the sum over parts is
-// the full VJP): symmetric kernels (eta = 0, and eta != 0 packed) -> the quads Q = part (mod nparts), written to all
-// rows; otherwise (ordered kernels) the row slice [part * ceil(M/nparts), ...) against all
-// columns, other rows zero.  Outputs plain (no epilogue).
-template <int D>
-int ode_self_bwd_part_d(const float* q, const float* p, const float* gv, const float* gmG,
-                        const float* gdiv, int64_t M, double sigma, double eta, int part,
-                        int nparts, float* gq, float* gp, void* ws, size_t wsb, hipStream_t st,
-                        const float* zs = nullptr, int64_t zr0 = 0, int64_t zn = 0) {
-  if (nparts == 1)  // the whole VJP: exactly the single-device kernel
-    return ode_self_bwd_d<D>(q, p, gv, gmG, gdiv, M, sigma, eta, make_outs(gq, gp), ws, wsb, st, zs, zr0, zn);
-  const bool b0 = gmG == nullptr;  // zero mG cotangent: symmetric packed kernels only
-  if (zs != nullptr && (eta != 0.0 || !(b0 || g_bwd_alg == 3))) {
-    set_error("ode_self_bwd_part: divergence rows (zs) need eta = 0 and the packed VJP (bwd_alg 3)");
-    return DICP_ERR_INVALID;
-  }
-  if (eta == 0.0 && (g_bwd_alg >= 2 || b0)) {
-    const float* gb = b0 ? gv : gmG;
-    Args a = {q, p, gv, gb, q, p, gv, gb, 0.f};
-    Scal sc = make_scal(sigma, 0.0);
+  bool raw = false;
+  if (!has_eta) {
     scale_coords(a, sc, sigma);
-    sc.dev0 = gdiv;
-    const bool pk = b0 || g_bwd_alg == 3;
-    const bool raw = tl_coord_raw != 0 && pk;
+    raw = tl_coord_raw != 0 && pk;   // packed kernels only
     if (raw) raw_coords(a, sc);
-    return launch_sym_bwd<D>(a, sc, M, make_outs(gq, gp), ws, wsb, st, part, nparts, pk, b0, zs, zr0,
-                             zn, raw);
   }
-  if (eta != 0.0 && g_bwd_eta_alg == 2) {  // symmetric packed eta VJP: quads Q = part (mod nparts)
-    const float* gb = b0 ? gv : gmG;
-    Args a = {q, p, gv, gb, q, p, gv, gb, 0.f};
-    Scal sc = make_scal(sigma, eta);
-    sc.dev0 = gdiv;
-    return launch_sym_bwd_eta<D>(a, sc, M, make_outs(gq, gp), ws, wsb, st, true, part, nparts, b0);
+  if (has_eta) {   // symmetric: parts only in the packed form
+    if (nparts == 1 ? g_bwd_eta_alg >= 1 : g_bwd_eta_alg == 2)
+      return launch_sym_bwd_eta<D>(a, sc, M, o, ws, wsb, st, g_bwd_eta_alg == 2, part, nparts, b0);
+  } else if (pk || g_bwd_alg == 2) {
+    return launch_sym_bwd<D>(a, sc, M, o, ws, wsb, st, part, nparts, pk, b0, zs, zr0, zn, raw);
   }
-  if (b0) {
-    set_error("ode_self_bwd_part: a NULL mG cotangent (zero) needs a symmetric packed kernel");
-    return DICP_ERR_INVALID;
+  int64_t rows = M;
+  if (nparts > 1) {   // the part's row slice, the other rows zero
+    if (int rc = no_batch("ode_self_bwd_part(ordered)")) return rc;
+    const int64_t per = (M + nparts - 1) / nparts;
+    const int64_t r0 = std::min(per * part, M), r1 = std::min(r0 + per, M);
+    if ((o.ptr[0] && hipMemsetAsync(o.ptr[0], 0, (size_t)M * D * sizeof(float), st) != hipSuccess) ||
+        hipMemsetAsync(o.ptr[1], 0, (size_t)M * D * sizeof(float), st) != hipSuccess) {
+      set_error("ode_self_bwd_part: hipMemsetAsync failed");
+      return DICP_ERR_HIP;
+    }
+    if (r1 <= r0) return DICP_OK;
+    rows = r1 - r0;
+    const int64_t o0 = r0 * D;
+    a.r0 += o0, a.r1 += o0, a.r2 += o0, a.r3 += o0;
+    if (o.ptr[0]) o.ptr[0] += o0;
+    o.ptr[1] += o0;
   }
-  if (int rc = no_batch("ode_self_bwd_part(ordered)")) return rc;
-  const int64_t per = (M + nparts - 1) / nparts;
-  const int64_t r0 = per * part < M ? per * part : M;
-  const int64_t r1 = r0 + per < M ? r0 + per : M;
-  if ((gq && hipMemsetAsync(gq, 0, (size_t)M * D * sizeof(float), st) != hipSuccess) ||
-      hipMemsetAsync(gp, 0, (size_t)M * D * sizeof(float), st) != hipSuccess) {
-    set_error("ode_self_bwd_part: hipMemsetAsync failed");
-    return DICP_ERR_HIP;
-  }
-  if (r1 <= r0) return DICP_OK;
-  const int64_t o0 = r0 * D;
-  Args a = {q + o0, p + o0, gv + o0, gmG + o0, q, p, gv, gmG, 0.f};
-  const Outs o = make_outs(gq ? gq + o0 : nullptr, gp + o0);
-  if (eta != 0.0) {
-    Scal sc = make_scal(sigma, eta);
-    sc.dev0 = gdiv;
-    return launch_r<OpOdeSelfBwdEta<D>>(r_bwd(), "ode_self_bwd_eta", a, sc, r1 - r0, M, o, ws, wsb, st);
-  }
-  Scal sc = make_scal(sigma, 0.0);
-  scale_coords(a, sc, sigma);
-  sc.dev0 = gdiv;
-  if (g_bwd_alg == 1)
-    return launch_r<OpOdeSelfBwd2<D>>(r_bwd(), "ode_self_bwd", a, sc, r1 - r0, M, o, ws, wsb, st);
-  return launch_r<OpOdeSelfBwd<D>>(r_bwd(), "ode_self_bwd", a, sc, r1 - r0, M, o, ws, wsb, st);
+  return visit_bwd_ord<D>(has_eta, g_bwd_alg, [&](auto t) {
+    return launch_r<op_of<decltype(t)>>(r_bwd(), has_eta ? "ode_self_bwd_eta" : "ode_self_bwd", a, sc, rows, M, o,
+                                        ws, wsb, st);
+  });
 }
 
-template <int D>
-size_t ode_self_bwd_part_ws(int64_t M, int nparts) {
-  const int64_t per = (M + nparts - 1) / nparts;
-  size_t m = sym_ws_bytes(M, 2 * D, nparts);
-  for (size_t v : {ws_r<OpOdeSelfBwd<D>>(r_bwd(), per, M), ws_r<OpOdeSelfBwdEta<D>>(r_bwd(), per, M),
-                   ws_r<OpOdeSelfBwd2<D>>(r_bwd(), per, M)})
-    m = v > m ? v : m;
-  return m;
+// the external-point forward with or without the eta terms and the divergence rows gx:
+// f(OpTag<scalar rows>, OpTag<packed rows>), ext_alg chooses between the two
+template <int D, class F>
+auto visit_ext_fwd(bool eta, bool gx, F&& f) {
+  return for_bool(eta, [&](auto e) {
+    return for_bool(gx, [&](auto g) {
+      constexpr bool kEta = decltype(e)::value, kG = decltype(g)::value;
+      return f(OpTag<OpOdeExtFwd<D, kEta, kG>>{}, OpTag<OpExtFwdPk<D, kEta, kG>>{});
+    });
+  });
 }
 
 template <int D>
@@ -663,41 +608,23 @@ int ode_ext_fwd_d(const float* x, int64_t N, const float* q, const float* p, int
                   hipStream_t st) {
   if (cx_eligible(N, M, true)) return cx_ext_fwd(x, N, q, p, M, D, sigma, eta, vx, gx, ws, wsb, st);
   const Outs o = make_outs(vx, gx);
-  if (g_ext_alg == 1) {
-    const Args a = {x, nullptr, nullptr, nullptr, q, p, nullptr, nullptr};
-    const Scal sc = make_scal(sigma, eta);
-    if (eta != 0.0)
-      return gx ? launch_rowred_pk<OpExtFwdPk<D, true, true>>("ode_ext_fwd", a, sc, N, M, o, ws, wsb, st)
-                : launch_rowred_pk<OpExtFwdPk<D, true, false>>("ode_ext_fwd", a, sc, N, M, o, ws, wsb, st);
-    return gx ? launch_rowred_pk<OpExtFwdPk<D, false, true>>("ode_ext_fwd", a, sc, N, M, o, ws, wsb, st)
-              : launch_rowred_pk<OpExtFwdPk<D, false, false>>("ode_ext_fwd", a, sc, N, M, o, ws, wsb, st);
-  }
   const Args a = {x, nullptr, nullptr, nullptr, q, p, nullptr, nullptr};
   const Scal sc = make_scal(sigma, eta);
-  if (eta != 0.0) {
-    if (gx) return launch_rowred<OpOdeExtFwd<D, true, true>, kR>("ode_ext_fwd", a, sc, N, M, o, ws, wsb, st);
-    return launch_rowred<OpOdeExtFwd<D, true, false>, kR>("ode_ext_fwd", a, sc, N, M, o, ws, wsb, st);
-  }
-  if (gx) return launch_rowred<OpOdeExtFwd<D, false, true>, kR>("ode_ext_fwd", a, sc, N, M, o, ws, wsb, st);
-  return launch_rowred<OpOdeExtFwd<D, false, false>, kR>("ode_ext_fwd", a, sc, N, M, o, ws, wsb, st);
+  return visit_ext_fwd<D>(eta != 0.0, gx != nullptr, [&](auto scalar, auto packed) {
+    return g_ext_alg == 1
+               ? launch_rowred_pk<op_of<decltype(packed)>>("ode_ext_fwd", a, sc, N, M, o, ws, wsb, st)
+               : launch_rowred<op_of<decltype(scalar)>, kR>("ode_ext_fwd", a, sc, N, M, o, ws, wsb, st);
+  });
 }
 
 template <int D>
 size_t ode_ext_fwd_ws(int64_t N, int64_t M) {
-  size_t m = 0;
-  for (size_t v : {rowred_ws_bytes<OpOdeExtFwd<D, true, true>, kR>(N, M),
-                   rowred_ws_bytes<OpOdeExtFwd<D, true, false>, kR>(N, M),
-                   rowred_ws_bytes<OpOdeExtFwd<D, false, true>, kR>(N, M),
-                   rowred_ws_bytes<OpOdeExtFwd<D, false, false>, kR>(N, M),
-                   rowred_pk_ws_bytes<OpExtFwdPk<D, true, true>>(N, M),
-                   rowred_pk_ws_bytes<OpExtFwdPk<D, true, false>>(N, M),
-                   rowred_pk_ws_bytes<OpExtFwdPk<D, false, true>>(N, M),
-                   rowred_pk_ws_bytes<OpExtFwdPk<D, false, false>>(N, M)})
-    m = v > m ? v : m;
-  if (cx_eligible(N, M, true)) {
-    const size_t c = cx_ext_ws(N, M, D);
-    m = c > m ? c : m;
-  }
+  size_t m = cx_eligible(N, M, true) ? cx_ext_ws(N, M, D) : 0;
+  for (int v = 0; v < 4; ++v)
+    visit_ext_fwd<D>((v & 1) != 0, (v & 2) != 0, [&](auto scalar, auto packed) {
+      m = std::max({m, rowred_ws_bytes<op_of<decltype(scalar)>, kR>(N, M),
+                    rowred_pk_ws_bytes<op_of<decltype(packed)>>(N, M)});
+    });
   return m;
 }
 
@@ -751,21 +678,117 @@ size_t ode_ext_bwd_ws(int64_t N, int64_t M) {
 
 }  // namespace
 
+// ---- what the entry points below share ----
+namespace {
+// The forward for entry point `entry`: rows [row0, row0 + nrows) (nrows < 0: all) in `order`.
+int self_fwd(const char* entry, int D, const float* q, const float* p, int64_t M, double sigma, double eta,
+             const Outs& o, void* ws, size_t wsb, dicp_stream_t stream, int64_t row0 = 0, int64_t nrows = -1,
+             const int32_t* order = nullptr, float* zs = nullptr) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  return with_dim(D, entry, [&](auto d) {
+    return ode_self_fwd_d<decltype(d)::value>(q, p, M, sigma, eta, o, ws, wsb, st, row0, nrows, order, zs);
+  });
+}
+
+// Outputs of an Euler step of the rows from row0: x_next = x + dt * (the pass's rows)
+Outs euler_outs(const float* q, const float* p, int64_t row0, int D, double dt, float* q_next, float* p_next,
+                float* g) {
+  Outs o = make_outs(q_next, p_next, g, nullptr);
+  o.base[0] = q + row0 * D;
+  o.base[1] = p + row0 * D;
+  o.alpha[0] = o.alpha[1] = (float)dt;
+  return o;
+}
+
+// The arguments of a row-slice entry: 0 <= row0, row0 + nrows <= M, sigma > 0 and, for a slice
+// with rows, every pointer of `need` and no output equal to one of its `others` (NULL: skipped).
+struct NoAlias {
+  const float* out;
+  const float* others[4];
+};
+int check_rows(const char* entry, int64_t M, int64_t row0, int64_t nrows, double sigma,
+               std::initializer_list<const void*> need, std::initializer_list<NoAlias> no_alias = {}) {
+  bool bad = M < 0 || row0 < 0 || nrows < 0 || row0 + nrows > M || !(sigma > 0);
+  if (nrows > 0) {
+    for (const void* ptr : need) bad = bad || ptr == nullptr;
+    for (const NoAlias& n : no_alias)
+      for (const float* x : n.others) bad = bad || (n.out != nullptr && n.out == x);
+  }
+  if (!bad) return DICP_OK;
+  set_error("%s: invalid arguments%s", entry, no_alias.size() ? " (outputs must not alias inputs)" : "");
+  return DICP_ERR_INVALID;
+}
+
+// p_next may be NULL: the momenta update is not wanted (the packed pass skips its Gs' / Hs /
+// GL' sums); zs may be NULL (no divergence rows)
+int euler_step_rows(const char* entry, const float* q, const float* p, int64_t M, int64_t row0, int64_t nrows,
+                    int D, double sigma, double eta, double dt, const int32_t* row_order, float* q_next,
+                    float* p_next, float* g, float* zs, void* ws, size_t ws_bytes, dicp_stream_t stream) {
+  if (int rc = check_rows(entry, M, row0, nrows, sigma, {q, p, q_next},
+                          {{q_next, {q, p}}, {p_next, {q, p}}, {zs, {q, p, q_next, p_next}}}))
+    return rc;
+  if (nrows == 0) return DICP_OK;
+  return self_fwd(entry, D, q, p, M, sigma, eta, euler_outs(q, p, row0, D, dt, q_next, p_next, g), ws, ws_bytes,
+                  stream, row0, nrows, row_order, zs);
+}
+
+// lq_next may be NULL: only lp_next is produced (the gq half of the eta = 0 symmetric VJP is
+// then never evaluated -- the last adjoint step when the start points need no gradient).
+// lp may be NULL: a zero cotangent on the momenta (the first adjoint step when the loss does
+// not depend on the final momenta; eta = 0), the b terms of the VJP are then skipped.
+// zs may be NULL (no divergence rows).
+int euler_adjoint_step(const char* entry, const float* q, const float* p, const float* lq, const float* lp,
+                       const float* gdiv, int64_t M, int D, double sigma, double eta, double dt,
+                       const float* addq, const float* addp, const float* zs, float* lq_next, float* lp_next,
+                       void* ws, size_t ws_bytes, dicp_stream_t stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  bool alias = false;
+  for (const float* x : {q, p, lq, lp, zs}) alias = alias || (x && ((lq_next && x == lq_next) || x == lp_next));
+  if (M < 0 || (M > 0 && (!q || !p || !lq || !lp_next || alias)) || !(sigma > 0)) {
+    set_error("%s: invalid arguments (outputs must not alias inputs)", entry);
+    return DICP_ERR_INVALID;
+  }
+  Outs o = make_outs(lq_next, lp_next);
+  o.base[0] = lq;
+  o.base[1] = lp;
+  o.add[0] = addq;
+  o.add[1] = addp;
+  o.alpha[0] = o.alpha[1] = (float)dt;
+  return with_dim(D, entry, [&](auto d) {
+    return ode_self_bwd_d<decltype(d)::value>(q, p, lq, lp, gdiv, M, sigma, eta, o, ws, ws_bytes, st, zs, 0, M);
+  });
+}
+
+// gq may be NULL (gp only), gmG NULL = zero cotangent; zs: divergence rows [zrow0, zrow0 + znrows)
+int self_bwd_part(const char* entry, const float* q, const float* p, const float* gv, const float* gmG,
+                  const float* gdiv, int64_t M, int D, double sigma, double eta, int part, int nparts,
+                  const float* zs, int64_t zrow0, int64_t znrows, float* gq, float* gp, void* ws,
+                  size_t ws_bytes, dicp_stream_t stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (M < 0 || nparts < 1 || part < 0 || part >= nparts || (M > 0 && (!q || !p || !gv || !gp)) ||
+      !(sigma > 0) || (zs && (zrow0 < 0 || znrows < 0 || zrow0 + znrows > M))) {
+    set_error("%s: invalid arguments", entry);
+    return DICP_ERR_INVALID;
+  }
+  if (M == 0) return DICP_OK;
+  return with_dim(D, entry, [&](auto d) {
+    return ode_self_bwd_d<decltype(d)::value>(q, p, gv, gmG, gdiv, M, sigma, eta, make_outs(gq, gp), ws, ws_bytes,
+                                              st, zs, zrow0, znrows, part, nparts);
+  });
+}
+}  // namespace
+
 extern "C" int dicp_lddmm_ode_self_fwd_f32(const float* q, const float* p, int64_t M, int D,
                                            double sigma, double eta, float* v, float* mG,
                                            float* g, float* h, void* ws, size_t ws_bytes,
                                            dicp_stream_t stream) {
   dicp::BatchCall batch_call_;  // a call of a launch batch (batch.hpp)
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (M < 0 || (M > 0 && (!q || !p || !v || !mG)) || !(sigma > 0)) {
     set_error("dicp_lddmm_ode_self_fwd_f32: invalid arguments");
     return DICP_ERR_INVALID;
   }
-  switch (D) {
-    case 2: return ode_self_fwd_d<2>(q, p, M, sigma, eta, make_outs(v, mG, g, h), ws, ws_bytes, st);
-    case 3: return ode_self_fwd_d<3>(q, p, M, sigma, eta, make_outs(v, mG, g, h), ws, ws_bytes, st);
-    default: set_error("ode_self_fwd: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
-  }
+  return self_fwd("dicp_lddmm_ode_self_fwd_f32", D, q, p, M, sigma, eta, make_outs(v, mG, g, h), ws, ws_bytes,
+                  stream);
 }
 
 extern "C" int dicp_lddmm_ode_self_bwd_f32(const float* q, const float* p, const float* gv,
@@ -779,11 +802,10 @@ extern "C" int dicp_lddmm_ode_self_bwd_f32(const float* q, const float* p, const
     set_error("dicp_lddmm_ode_self_bwd_f32: invalid arguments");
     return DICP_ERR_INVALID;
   }
-  switch (D) {
-    case 2: return ode_self_bwd_d<2>(q, p, gv, gmG, gdiv, M, sigma, eta, make_outs(gq, gp), ws, ws_bytes, st);
-    case 3: return ode_self_bwd_d<3>(q, p, gv, gmG, gdiv, M, sigma, eta, make_outs(gq, gp), ws, ws_bytes, st);
-    default: set_error("ode_self_bwd: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
-  }
+  return with_dim(D, "dicp_lddmm_ode_self_bwd_f32", [&](auto d) {
+    return ode_self_bwd_d<decltype(d)::value>(q, p, gv, gmG, gdiv, M, sigma, eta, make_outs(gq, gp), ws, ws_bytes,
+                                              st);
+  });
 }
 
 // One explicit-Euler step of the shooting ODE with the state update fused into the
@@ -794,21 +816,13 @@ extern "C" int dicp_lddmm_euler_step_f32(const float* q, const float* p, int64_t
                                          float* p_next, float* g, void* ws, size_t ws_bytes,
                                          dicp_stream_t stream) {
   dicp::BatchCall batch_call_;  // a call of a launch batch (batch.hpp)
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (M < 0 || (M > 0 && (!q || !p || !q_next || !p_next)) || !(sigma > 0) ||
       (M > 0 && (q_next == q || q_next == p || p_next == q || p_next == p))) {
     set_error("dicp_lddmm_euler_step_f32: invalid arguments (outputs must not alias inputs)");
     return DICP_ERR_INVALID;
   }
-  Outs o = make_outs(q_next, p_next, g, nullptr);
-  o.base[0] = q;
-  o.base[1] = p;
-  o.alpha[0] = o.alpha[1] = (float)dt;
-  switch (D) {
-    case 2: return ode_self_fwd_d<2>(q, p, M, sigma, eta, o, ws, ws_bytes, st);
-    case 3: return ode_self_fwd_d<3>(q, p, M, sigma, eta, o, ws, ws_bytes, st);
-    default: set_error("euler_step: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
-  }
+  return self_fwd("dicp_lddmm_euler_step_f32", D, q, p, M, sigma, eta,
+                  euler_outs(q, p, 0, D, dt, q_next, p_next, g), ws, ws_bytes, stream);
 }
 
 // The matching adjoint step (exact discrete adjoint of the Euler step):
@@ -822,30 +836,8 @@ extern "C" int dicp_lddmm_euler_adjoint_step_zs_f32(const float* q, const float*
                                                     const float* zs, float* lq_next, float* lp_next,
                                                     void* ws, size_t ws_bytes, dicp_stream_t stream) {
   dicp::BatchCall batch_call_;  // a call of a launch batch (batch.hpp)
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const float* ins[5] = {q, p, lq, lp, zs};
-  bool alias = false;
-  for (const float* x : ins) alias = alias || (x && ((lq_next && x == lq_next) || x == lp_next));
-  // lq_next may be NULL: only lp_next is produced (the gq half of the eta = 0 symmetric VJP is
-  // then never evaluated -- the last adjoint step when the start points need no gradient).
-  // lp may be NULL: a zero cotangent on the momenta (the first adjoint step when the loss does
-  // not depend on the final momenta; eta = 0), the b terms of the VJP are then skipped.
-  // zs may be NULL (no divergence rows).
-  if (M < 0 || (M > 0 && (!q || !p || !lq || !lp_next || alias)) || !(sigma > 0)) {
-    set_error("dicp_lddmm_euler_adjoint_step_f32: invalid arguments (outputs must not alias inputs)");
-    return DICP_ERR_INVALID;
-  }
-  Outs o = make_outs(lq_next, lp_next);
-  o.base[0] = lq;
-  o.base[1] = lp;
-  o.add[0] = addq;
-  o.add[1] = addp;
-  o.alpha[0] = o.alpha[1] = (float)dt;
-  switch (D) {
-    case 2: return ode_self_bwd_d<2>(q, p, lq, lp, gdiv, M, sigma, eta, o, ws, ws_bytes, st, zs, 0, M);
-    case 3: return ode_self_bwd_d<3>(q, p, lq, lp, gdiv, M, sigma, eta, o, ws, ws_bytes, st, zs, 0, M);
-    default: set_error("euler_adjoint_step: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
-  }
+  return euler_adjoint_step("dicp_lddmm_euler_adjoint_step_zs_f32", q, p, lq, lp, gdiv, M, D, sigma, eta, dt, addq,
+                            addp, zs, lq_next, lp_next, ws, ws_bytes, stream);
 }
 
 extern "C" int dicp_lddmm_euler_adjoint_step_f32(const float* q, const float* p, const float* lq,
@@ -855,8 +847,8 @@ extern "C" int dicp_lddmm_euler_adjoint_step_f32(const float* q, const float* p,
                                                  float* lq_next, float* lp_next, void* ws,
                                                  size_t ws_bytes, dicp_stream_t stream) {
   dicp::BatchCall batch_call_;  // a call of a launch batch (batch.hpp)
-  return dicp_lddmm_euler_adjoint_step_zs_f32(q, p, lq, lp, gdiv, M, D, sigma, eta, dt, addq, addp, nullptr,
-                                              lq_next, lp_next, ws, ws_bytes, stream);
+  return euler_adjoint_step("dicp_lddmm_euler_adjoint_step_f32", q, p, lq, lp, gdiv, M, D, sigma, eta, dt, addq,
+                            addp, nullptr, lq_next, lp_next, ws, ws_bytes, stream);
 }
 
 extern "C" int dicp_lddmm_ode_ext_fwd_f32(const float* x, int64_t N, const float* q,
@@ -869,11 +861,9 @@ extern "C" int dicp_lddmm_ode_ext_fwd_f32(const float* x, int64_t N, const float
     set_error("dicp_lddmm_ode_ext_fwd_f32: invalid arguments");
     return DICP_ERR_INVALID;
   }
-  switch (D) {
-    case 2: return ode_ext_fwd_d<2>(x, N, q, p, M, sigma, eta, vx, gx, ws, ws_bytes, st);
-    case 3: return ode_ext_fwd_d<3>(x, N, q, p, M, sigma, eta, vx, gx, ws, ws_bytes, st);
-    default: set_error("ode_ext_fwd: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
-  }
+  return with_dim(D, "dicp_lddmm_ode_ext_fwd_f32", [&](auto d) {
+    return ode_ext_fwd_d<decltype(d)::value>(x, N, q, p, M, sigma, eta, vx, gx, ws, ws_bytes, st);
+  });
 }
 
 extern "C" int dicp_lddmm_ode_ext_bwd_f32(const float* x, int64_t N, const float* q,
@@ -888,11 +878,9 @@ extern "C" int dicp_lddmm_ode_ext_bwd_f32(const float* x, int64_t N, const float
     set_error("dicp_lddmm_ode_ext_bwd_f32: invalid arguments");
     return DICP_ERR_INVALID;
   }
-  switch (D) {
-    case 2: return ode_ext_bwd_d<2>(x, N, q, p, M, sigma, eta, gvx, gdiv, gxo, gq, gp, ws, ws_bytes, st);
-    case 3: return ode_ext_bwd_d<3>(x, N, q, p, M, sigma, eta, gvx, gdiv, gxo, gq, gp, ws, ws_bytes, st);
-    default: set_error("ode_ext_bwd: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
-  }
+  return with_dim(D, "dicp_lddmm_ode_ext_bwd_f32", [&](auto d) {
+    return ode_ext_bwd_d<decltype(d)::value>(x, N, q, p, M, sigma, eta, gvx, gdiv, gxo, gq, gp, ws, ws_bytes, st);
+  });
 }
 
 // Row-split (multi-GPU single frame): rows [row0, row0 + nrows) of the fused
@@ -903,18 +891,10 @@ extern "C" int dicp_lddmm_ode_self_fwd_rows_f32(const float* q, const float* p, 
                                                 float* g, float* h, void* ws, size_t ws_bytes,
                                                 dicp_stream_t stream) {
   dicp::BatchCall batch_call_;  // a call of a launch batch (batch.hpp)
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (M < 0 || row0 < 0 || nrows < 0 || row0 + nrows > M ||
-      (nrows > 0 && (!q || !p || !v || !mG)) || !(sigma > 0)) {
-    set_error("dicp_lddmm_ode_self_fwd_rows_f32: invalid arguments");
-    return DICP_ERR_INVALID;
-  }
+  const char* entry = "dicp_lddmm_ode_self_fwd_rows_f32";
+  if (int rc = check_rows(entry, M, row0, nrows, sigma, {q, p, v, mG})) return rc;
   if (nrows == 0) return DICP_OK;
-  switch (D) {
-    case 2: return ode_self_fwd_d<2>(q, p, M, sigma, eta, make_outs(v, mG, g, h), ws, ws_bytes, st, row0, nrows);
-    case 3: return ode_self_fwd_d<3>(q, p, M, sigma, eta, make_outs(v, mG, g, h), ws, ws_bytes, st, row0, nrows);
-    default: set_error("ode_self_fwd_rows: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
-  }
+  return self_fwd(entry, D, q, p, M, sigma, eta, make_outs(v, mG, g, h), ws, ws_bytes, stream, row0, nrows);
 }
 
 extern "C" int dicp_lddmm_euler_step_rows_f32(const float* q, const float* p, int64_t M,
@@ -923,22 +903,11 @@ extern "C" int dicp_lddmm_euler_step_rows_f32(const float* q, const float* p, in
                                               float* p_next, float* g, void* ws,
                                               size_t ws_bytes, dicp_stream_t stream) {
   dicp::BatchCall batch_call_;  // a call of a launch batch (batch.hpp)
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (M < 0 || row0 < 0 || nrows < 0 || row0 + nrows > M ||
-      (nrows > 0 && (!q || !p || !q_next || !p_next)) || !(sigma > 0)) {
-    set_error("dicp_lddmm_euler_step_rows_f32: invalid arguments");
-    return DICP_ERR_INVALID;
-  }
+  const char* entry = "dicp_lddmm_euler_step_rows_f32";
+  if (int rc = check_rows(entry, M, row0, nrows, sigma, {q, p, q_next, p_next})) return rc;
   if (nrows == 0) return DICP_OK;
-  Outs o = make_outs(q_next, p_next, g, nullptr);
-  o.base[0] = q + row0 * D;
-  o.base[1] = p + row0 * D;
-  o.alpha[0] = o.alpha[1] = (float)dt;
-  switch (D) {
-    case 2: return ode_self_fwd_d<2>(q, p, M, sigma, eta, o, ws, ws_bytes, st, row0, nrows);
-    case 3: return ode_self_fwd_d<3>(q, p, M, sigma, eta, o, ws, ws_bytes, st, row0, nrows);
-    default: set_error("euler_step_rows: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
-  }
+  return self_fwd(entry, D, q, p, M, sigma, eta, euler_outs(q, p, row0, D, dt, q_next, p_next, g), ws, ws_bytes,
+                  stream, row0, nrows);
 }
 
 // Ordered forms (rows [row0, row0 + nrows) visited in row_order, or NULL = natural order):
@@ -948,18 +917,11 @@ extern "C" int dicp_lddmm_ode_self_fwd_zs_f32(const float* q, const float* p, in
                                               const int32_t* row_order, float* v, float* mG, float* g,
                                               float* zs, void* ws, size_t ws_bytes, dicp_stream_t stream) {
   dicp::BatchCall batch_call_;  // a call of a launch batch (batch.hpp)
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (M < 0 || row0 < 0 || nrows < 0 || row0 + nrows > M ||
-      (nrows > 0 && (!q || !p || !v || !mG || !zs)) || !(sigma > 0)) {
-    set_error("dicp_lddmm_ode_self_fwd_zs_f32: invalid arguments");
-    return DICP_ERR_INVALID;
-  }
+  const char* entry = "dicp_lddmm_ode_self_fwd_zs_f32";
+  if (int rc = check_rows(entry, M, row0, nrows, sigma, {q, p, v, mG, zs})) return rc;
   if (nrows == 0) return DICP_OK;
-  switch (D) {
-    case 2: return ode_self_fwd_d<2>(q, p, M, sigma, eta, make_outs(v, mG, g, nullptr), ws, ws_bytes, st, row0, nrows, row_order, zs);
-    case 3: return ode_self_fwd_d<3>(q, p, M, sigma, eta, make_outs(v, mG, g, nullptr), ws, ws_bytes, st, row0, nrows, row_order, zs);
-    default: set_error("ode_self_fwd_zs: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
-  }
+  return self_fwd(entry, D, q, p, M, sigma, eta, make_outs(v, mG, g, nullptr), ws, ws_bytes, stream, row0, nrows,
+                  row_order, zs);
 }
 
 extern "C" int dicp_lddmm_ode_self_fwd_ord_f32(const float* q, const float* p, int64_t M,
@@ -968,18 +930,11 @@ extern "C" int dicp_lddmm_ode_self_fwd_ord_f32(const float* q, const float* p, i
                                                float* mG, float* g, float* h, void* ws,
                                                size_t ws_bytes, dicp_stream_t stream) {
   dicp::BatchCall batch_call_;  // a call of a launch batch (batch.hpp)
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (M < 0 || row0 < 0 || nrows < 0 || row0 + nrows > M ||
-      (nrows > 0 && (!q || !p || !v || !mG)) || !(sigma > 0)) {
-    set_error("dicp_lddmm_ode_self_fwd_ord_f32: invalid arguments");
-    return DICP_ERR_INVALID;
-  }
+  const char* entry = "dicp_lddmm_ode_self_fwd_ord_f32";
+  if (int rc = check_rows(entry, M, row0, nrows, sigma, {q, p, v, mG})) return rc;
   if (nrows == 0) return DICP_OK;
-  switch (D) {
-    case 2: return ode_self_fwd_d<2>(q, p, M, sigma, eta, make_outs(v, mG, g, h), ws, ws_bytes, st, row0, nrows, row_order);
-    case 3: return ode_self_fwd_d<3>(q, p, M, sigma, eta, make_outs(v, mG, g, h), ws, ws_bytes, st, row0, nrows, row_order);
-    default: set_error("ode_self_fwd_ord: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
-  }
+  return self_fwd(entry, D, q, p, M, sigma, eta, make_outs(v, mG, g, h), ws, ws_bytes, stream, row0, nrows,
+                  row_order);
 }
 
 extern "C" int dicp_lddmm_euler_step_zs_f32(const float* q, const float* p, int64_t M, int64_t row0,
@@ -988,26 +943,18 @@ extern "C" int dicp_lddmm_euler_step_zs_f32(const float* q, const float* p, int6
                                             float* g, float* zs, void* ws, size_t ws_bytes,
                                             dicp_stream_t stream) {
   dicp::BatchCall batch_call_;  // a call of a launch batch (batch.hpp)
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // p_next may be NULL: the momenta update is not wanted (the packed pass skips its Gs' / Hs /
-  // GL' sums); zs may be NULL (no divergence rows)
-  if (M < 0 || row0 < 0 || nrows < 0 || row0 + nrows > M ||
-      (nrows > 0 && (!q || !p || !q_next)) || !(sigma > 0) ||
-      (nrows > 0 && (q_next == q || q_next == p || (p_next && (p_next == q || p_next == p)) ||
-                     (zs && (zs == q || zs == p || zs == q_next || zs == p_next))))) {
-    set_error("dicp_lddmm_euler_step_ord_f32: invalid arguments (outputs must not alias inputs)");
-    return DICP_ERR_INVALID;
-  }
-  if (nrows == 0) return DICP_OK;
-  Outs o = make_outs(q_next, p_next, g, nullptr);
-  o.base[0] = q + row0 * D;
-  o.base[1] = p + row0 * D;
-  o.alpha[0] = o.alpha[1] = (float)dt;
-  switch (D) {
-    case 2: return ode_self_fwd_d<2>(q, p, M, sigma, eta, o, ws, ws_bytes, st, row0, nrows, row_order, zs);
-    case 3: return ode_self_fwd_d<3>(q, p, M, sigma, eta, o, ws, ws_bytes, st, row0, nrows, row_order, zs);
-    default: set_error("euler_step_ord: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
-  }
+  return euler_step_rows("dicp_lddmm_euler_step_zs_f32", q, p, M, row0, nrows, D, sigma, eta, dt, row_order, q_next,
+                         p_next, g, zs, ws, ws_bytes, stream);
+}
+
+extern "C" int dicp_lddmm_euler_step_ord_f32(const float* q, const float* p, int64_t M,
+                                             int64_t row0, int64_t nrows, int D, double sigma,
+                                             double eta, double dt, const int32_t* row_order,
+                                             float* q_next, float* p_next, float* g, void* ws,
+                                             size_t ws_bytes, dicp_stream_t stream) {
+  dicp::BatchCall batch_call_;  // a call of a launch batch (batch.hpp)
+  return euler_step_rows("dicp_lddmm_euler_step_ord_f32", q, p, M, row0, nrows, D, sigma, eta, dt, row_order, q_next,
+                         p_next, g, nullptr, ws, ws_bytes, stream);
 }
 
 // ---- the fused steps with the Gaussian cutoff of far tile pairs (lddmm_sym.hpp kCutTile) ----
@@ -1041,11 +988,8 @@ extern "C" int dicp_pair_boxes_f32(const float* q, int64_t M, int D, double sigm
     set_error("dicp_pair_boxes_f32: invalid arguments");
     return DICP_ERR_INVALID;
   }
-  switch (D) {
-    case 2: return pair_boxes_d<2>(q, M, sigma, boxes, st);
-    case 3: return pair_boxes_d<3>(q, M, sigma, boxes, st);
-    default: set_error("pair_boxes: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
-  }
+  return with_dim(D, "dicp_pair_boxes_f32",
+                  [&](auto d) { return pair_boxes_d<decltype(d)::value>(q, M, sigma, boxes, st); });
 }
 
 extern "C" int dicp_lddmm_ode_self_fwd_box_f32(const float* q, const float* p, int64_t M, int D, double sigma,
@@ -1087,16 +1031,6 @@ extern "C" int dicp_lddmm_euler_adjoint_step_box_f32(const float* q, const float
                                               lp_next, ws, ws_bytes, stream);
 }
 
-extern "C" int dicp_lddmm_euler_step_ord_f32(const float* q, const float* p, int64_t M,
-                                             int64_t row0, int64_t nrows, int D, double sigma,
-                                             double eta, double dt, const int32_t* row_order,
-                                             float* q_next, float* p_next, float* g, void* ws,
-                                             size_t ws_bytes, dicp_stream_t stream) {
-  dicp::BatchCall batch_call_;  // a call of a launch batch (batch.hpp)
-  return dicp_lddmm_euler_step_zs_f32(q, p, M, row0, nrows, D, sigma, eta, dt, row_order, q_next, p_next, g,
-                                      nullptr, ws, ws_bytes, stream);
-}
-
 // A row-split Euler step in two column phases (core/shooting.py, RowSplit.overlap): phase 0
 // runs the rank's rows against its own slice -- the rows' values, which the rank holds before
 // the all-gather of the step's input has landed -- into the first partial slots of `ws`;
@@ -1107,88 +1041,30 @@ extern "C" int dicp_lddmm_euler_step_ord_f32(const float* q, const float* p, int
 // step's up to fp32 summation order (and the coordinate origin of each phase: its first
 // column point).  Ordered packed passes (fwd_alg 2, 5, 6); zs needs eta = 0.
 namespace {
-template <class Op>
-int step_phase_op(const char* name, int phase, const Args& a0, const Args& a1, const Scal& sc, int64_t nrows,
-                  int64_t M, int64_t coff, const Outs& o, void* ws, size_t wsb, hipStream_t st) {
-  // phase 0 reads its nrows columns in place (no offset); phase 1 from coff, wrapping at M
-  return launch_pk_phase<Op>(name, phase, phase == 0 ? a0 : a1, sc, nrows, nrows, M - nrows,
-                             phase == 0 ? 0 : coff, phase == 0 ? nrows : M, o, ws, wsb, st);
-}
-
-struct PhaseGo {
-  int phase;
-  const Args &a0, &a1;
-  const Scal& sc;
-  int64_t nrows, M, coff;
-  const Outs& o;
-  void* ws;
-  size_t wsb;
-  hipStream_t st;
-  template <class OpS, class OpR>
-  int run(bool raw) const {
-    return raw ? step_phase_op<OpR>("ode_self_fwd(pk, phase)", phase, a0, a1, sc, nrows, M, coff, o, ws, wsb, st)
-               : step_phase_op<OpS>("ode_self_fwd(pk, phase)", phase, a0, a1, sc, nrows, M, coff, o, ws, wsb, st);
-  }
-};
-
-// the pass (and its raw-coordinate twin) for these outputs: f.run<OpScaled, OpRaw>(raw)
-template <int D, class F>
-int step_phase_pick(bool raw, bool zs, bool eta, bool mg, bool div, const F& f) {
-  if (zs)
-    return mg ? f.template run<OpOdeSelfFwdPk<D, true, false, true, true>, OpOdeSelfFwdPk<D, true, false, true, true, true>>(raw)
-              : f.template run<OpOdeSelfFwdPk<D, true, false, false, true>, OpOdeSelfFwdPk<D, true, false, false, true, true>>(raw);
-  if (eta)
-    return mg ? f.template run<OpOdeSelfFwdPk<D, true, true>, OpOdeSelfFwdPk<D, true, true, true, false, true>>(raw)
-              : f.template run<OpOdeSelfFwdPk<D, true, true, false>, OpOdeSelfFwdPk<D, true, true, false, false, true>>(raw);
-  if (!mg)
-    return div ? f.template run<OpOdeSelfFwdPk<D, true, false, false>, OpOdeSelfFwdPk<D, true, false, false, false, true>>(raw)
-               : f.template run<OpOdeSelfFwdPk<D, false, false, false>, OpOdeSelfFwdPk<D, false, false, false, false, true>>(raw);
-  return div ? f.template run<OpOdeSelfFwdPk<D, true>, OpOdeSelfFwdPk<D, true, false, true, false, true>>(raw)
-             : f.template run<OpOdeSelfFwdPk<D, false>, OpOdeSelfFwdPk<D, false, false, true, false, true>>(raw);
-}
-
 template <int D>
 int euler_step_phase_d(int phase, const float* q_loc, const float* p_loc, const float* q, const float* p, int64_t M,
                        int64_t row0, int64_t nrows, double sigma, double eta, const Outs& o, void* ws, size_t wsb,
                        hipStream_t st) {
-  Scal sc0 = make_scal(sigma, eta), sc1 = sc0;
-  // phase 0: rows = columns = the local slice; phase 1: rows = the slice of (q, p), columns =
-  // all of (q, p) read from row0 + nrows on (wrapping), M - nrows of them
-  Args a0 = {q_loc, p_loc, nullptr, nullptr, q_loc, p_loc, nullptr, nullptr, 0.f};
-  Args a1 = {q ? q + row0 * D : nullptr, p ? p + row0 * D : nullptr, nullptr, nullptr, q, p, nullptr, nullptr, 0.f};
-  const bool raw = tl_coord_raw != 0;
-  scale_coords(a0, sc0, sigma);
-  scale_coords(a1, sc1, sigma);
-  if (raw) {
-    raw_coords(a0, sc0);
-    raw_coords(a1, sc1);
-  }
-  const Scal& sc = phase == 0 ? sc0 : sc1;
-  const int64_t coff = row0 + nrows < M ? row0 + nrows : 0;
-  const PhaseGo go{phase, a0, a1, sc, nrows, M, coff, o, ws, wsb, st};
-  return step_phase_pick<D>(raw, o.ptr[3] != nullptr, eta != 0.0, o.ptr[1] != nullptr, o.ptr[2] != nullptr, go);
+  // phase 0: rows = columns = the local slice, read in place; phase 1: rows = the slice of
+  // (q, p), columns = all of (q, p) read from row0 + nrows on (wrapping), M - nrows of them
+  Args a = {q_loc, p_loc, nullptr, nullptr, q_loc, p_loc, nullptr, nullptr, 0.f};
+  if (phase == 1) a = {q + row0 * D, p + row0 * D, nullptr, nullptr, q, p, nullptr, nullptr, 0.f};
+  Scal sc = make_scal(sigma, eta);
+  const PkFwd v = {o.ptr[2] != nullptr, eta != 0.0, o.ptr[1] != nullptr, o.ptr[3] != nullptr, tl_coord_raw != 0};
+  scale_coords(a, sc, sigma);
+  if (v.raw) raw_coords(a, sc);
+  const int64_t coff = phase == 0 || row0 + nrows >= M ? 0 : row0 + nrows;
+  return visit_pk_fwd<D>(v, [&](auto t) {
+    return launch_pk_phase<op_of<decltype(t)>>("ode_self_fwd(pk, phase)", phase, a, sc, nrows, nrows, M - nrows, coff,
+                                               phase == 0 ? nrows : M, o, ws, wsb, st);
+  });
 }
 
 template <int D>
 size_t euler_step_phase_ws(int64_t nrows, int64_t M) {
   size_t m = 0;
-  for (size_t v : {pk_phase_ws_bytes<OpOdeSelfFwdPk<D, true, false, true, true>>(nrows, nrows, M - nrows),
-                   pk_phase_ws_bytes<OpOdeSelfFwdPk<D, true, false, true, true, true>>(nrows, nrows, M - nrows),
-                   pk_phase_ws_bytes<OpOdeSelfFwdPk<D, true, false, false, true>>(nrows, nrows, M - nrows),
-                   pk_phase_ws_bytes<OpOdeSelfFwdPk<D, true, false, false, true, true>>(nrows, nrows, M - nrows),
-                   pk_phase_ws_bytes<OpOdeSelfFwdPk<D, true, true>>(nrows, nrows, M - nrows),
-                   pk_phase_ws_bytes<OpOdeSelfFwdPk<D, true, true, true, false, true>>(nrows, nrows, M - nrows),
-                   pk_phase_ws_bytes<OpOdeSelfFwdPk<D, true, true, false>>(nrows, nrows, M - nrows),
-                   pk_phase_ws_bytes<OpOdeSelfFwdPk<D, true, true, false, false, true>>(nrows, nrows, M - nrows),
-                   pk_phase_ws_bytes<OpOdeSelfFwdPk<D, true, false, false>>(nrows, nrows, M - nrows),
-                   pk_phase_ws_bytes<OpOdeSelfFwdPk<D, true, false, false, false, true>>(nrows, nrows, M - nrows),
-                   pk_phase_ws_bytes<OpOdeSelfFwdPk<D, false, false, false>>(nrows, nrows, M - nrows),
-                   pk_phase_ws_bytes<OpOdeSelfFwdPk<D, false, false, false, false, true>>(nrows, nrows, M - nrows),
-                   pk_phase_ws_bytes<OpOdeSelfFwdPk<D, true>>(nrows, nrows, M - nrows),
-                   pk_phase_ws_bytes<OpOdeSelfFwdPk<D, true, false, true, false, true>>(nrows, nrows, M - nrows),
-                   pk_phase_ws_bytes<OpOdeSelfFwdPk<D, false>>(nrows, nrows, M - nrows),
-                   pk_phase_ws_bytes<OpOdeSelfFwdPk<D, false, false, true, false, true>>(nrows, nrows, M - nrows)})
-    m = v > m ? v : m;
+  for_each_pk_fwd<D>(
+      [&](auto t) { m = std::max(m, pk_phase_ws_bytes<op_of<decltype(t)>>(nrows, nrows, M - nrows)); });
   return m;
 }
 }  // namespace
@@ -1218,7 +1094,7 @@ extern "C" int dicp_lddmm_euler_step_phase_f32(int phase, const float* q_loc, co
               "not overlap the inputs, zs needs eta = 0)");
     return DICP_ERR_INVALID;
   }
-  if (!packed_fwd_alg()) {
+  if (!packed_fwd_alg(g_fwd_alg)) {
     set_error("dicp_lddmm_euler_step_phase_f32: needs an ordered packed forward (fwd_alg 2, 5 or 6)");
     return DICP_ERR_UNSUPPORTED;
   }
@@ -1229,11 +1105,10 @@ extern "C" int dicp_lddmm_euler_step_phase_f32(int phase, const float* q_loc, co
     o.base[0] = q + row0 * D;
     o.base[1] = p_next ? p + row0 * D : nullptr;
   }
-  switch (D) {
-    case 2: return euler_step_phase_d<2>(phase, q_loc, p_loc, q, p, M, row0, nrows, sigma, eta, o, ws, ws_bytes, st);
-    case 3: return euler_step_phase_d<3>(phase, q_loc, p_loc, q, p, M, row0, nrows, sigma, eta, o, ws, ws_bytes, st);
-    default: set_error("euler_step_phase: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
-  }
+  return with_dim(D, "dicp_lddmm_euler_step_phase_f32", [&](auto d) {
+    return euler_step_phase_d<decltype(d)::value>(phase, q_loc, p_loc, q, p, M, row0, nrows, sigma, eta, o, ws,
+                                                  ws_bytes, st);
+  });
 }
 
 extern "C" int dicp_lddmm_ode_self_bwd_part_zs_f32(const float* q, const float* p, const float* gv,
@@ -1243,19 +1118,8 @@ extern "C" int dicp_lddmm_ode_self_bwd_part_zs_f32(const float* q, const float* 
                                                    int64_t znrows, float* gq, float* gp, void* ws,
                                                    size_t ws_bytes, dicp_stream_t stream) {
   dicp::BatchCall batch_call_;  // a call of a launch batch (batch.hpp)
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (M < 0 || nparts < 1 || part < 0 || part >= nparts ||
-      (M > 0 && (!q || !p || !gv || !gp)) || !(sigma > 0) ||  // gq may be NULL (gp only), gmG NULL = 0
-      (zs && (zrow0 < 0 || znrows < 0 || zrow0 + znrows > M))) {
-    set_error("dicp_lddmm_ode_self_bwd_part_f32: invalid arguments");
-    return DICP_ERR_INVALID;
-  }
-  if (M == 0) return DICP_OK;
-  switch (D) {
-    case 2: return ode_self_bwd_part_d<2>(q, p, gv, gmG, gdiv, M, sigma, eta, part, nparts, gq, gp, ws, ws_bytes, st, zs, zrow0, znrows);
-    case 3: return ode_self_bwd_part_d<3>(q, p, gv, gmG, gdiv, M, sigma, eta, part, nparts, gq, gp, ws, ws_bytes, st, zs, zrow0, znrows);
-    default: set_error("ode_self_bwd_part: D=%d unsupported", D); return DICP_ERR_UNSUPPORTED;
-  }
+  return self_bwd_part("dicp_lddmm_ode_self_bwd_part_zs_f32", q, p, gv, gmG, gdiv, M, D, sigma, eta, part, nparts,
+                       zs, zrow0, znrows, gq, gp, ws, ws_bytes, stream);
 }
 
 extern "C" int dicp_lddmm_ode_self_bwd_part_f32(const float* q, const float* p, const float* gv,
@@ -1264,72 +1128,51 @@ extern "C" int dicp_lddmm_ode_self_bwd_part_f32(const float* q, const float* p, 
                                                 int nparts, float* gq, float* gp, void* ws,
                                                 size_t ws_bytes, dicp_stream_t stream) {
   dicp::BatchCall batch_call_;  // a call of a launch batch (batch.hpp)
-  return dicp_lddmm_ode_self_bwd_part_zs_f32(q, p, gv, gmG, gdiv, M, D, sigma, eta, part, nparts, nullptr, 0, 0,
-                                             gq, gp, ws, ws_bytes, stream);
+  return self_bwd_part("dicp_lddmm_ode_self_bwd_part_f32", q, p, gv, gmG, gdiv, M, D, sigma, eta, part, nparts,
+                       nullptr, 0, 0, gq, gp, ws, ws_bytes, stream);
 }
 
 // Workspace sizes for the LDDMM entries (the GMM ones live in gmm.hip).
 size_t dicp_lddmm_ws(int kind, int64_t M, int64_t N, int D) {
   if (!supported_dim(D)) return 0;
-  switch (kind) {
-    case DICP_WS_RED: {
-      size_t m = 0;
-      size_t c[] = {red_ws<OpKBase>(D, M, N), red_ws<OpKRed>(D, M, N), red_ws<OpGradK>(D, M, N),
-                    red_ws<OpGenDK>(D, M, N), red_ws<OpHessK>(D, M, N), red_ws<OpLapK>(D, M, N),
-                    red_ws<OpGradLapKPlain>(D, M, N), red_ws<OpGradKScal>(D, M, N),
-                    red_ws<OpMinSqDist>(D, M, N), red_ws<OpZDotB>(D, M, N),
-                    red_ws<OpDDK>(D, M, N), red_ws<OpKRedScal>(D, M, N),
-                    red_ws<OpGradLapKScal>(D, M, N), red_ws<OpMinSqDistOther>(D, M, N),
-                    red_ws<OpRadiusCount>(D, M, N),
-                    D == 2 ? rowred_pk_ws_bytes<OpExtFwdPk<2, false, false>>(M, N)
-                           : rowred_pk_ws_bytes<OpExtFwdPk<3, false, false>>(M, N)};
-      for (size_t v : c) m = v > m ? v : m;
-      if (cx_eligible(M, N) || (M == N && sym_red() == 2)) {   // (sym_red 2: x = y forced)
-        const size_t v = cx_red_ws(M, N, D);
-        m = v > m ? v : m;
+  return for_dim(D, [&](auto d) -> size_t {
+    constexpr int kD = decltype(d)::value;
+    switch (kind) {
+      case DICP_WS_RED: {
+        size_t m = max_of({red_ws<OpKBase>(D, M, N), red_ws<OpKRed>(D, M, N), red_ws<OpGradK>(D, M, N),
+                           red_ws<OpGenDK>(D, M, N), red_ws<OpHessK>(D, M, N), red_ws<OpLapK>(D, M, N),
+                           red_ws<OpGradLapKPlain>(D, M, N), red_ws<OpGradKScal>(D, M, N),
+                           red_ws<OpMinSqDist>(D, M, N), red_ws<OpZDotB>(D, M, N), red_ws<OpDDK>(D, M, N),
+                           red_ws<OpKRedScal>(D, M, N), red_ws<OpGradLapKScal>(D, M, N),
+                           red_ws<OpMinSqDistOther>(D, M, N), red_ws<OpRadiusCount>(D, M, N),
+                           rowred_pk_ws_bytes<OpExtFwdPk<kD, false, false>>(M, N)});
+        if (cx_eligible(M, N) || (M == N && sym_red() == 2))   // (sym_red 2: x = y forced)
+          m = std::max(m, cx_red_ws(M, N, D));
+        return m;
       }
-      return m;
+      case DICP_WS_ODE_SELF_FWD: return ode_self_fwd_rows_ws<kD>(M, M);
+      case DICP_WS_ODE_SELF_BWD: return ode_self_bwd_ws<kD>(M, 1);
+      case DICP_WS_ODE_EXT_FWD: return ode_ext_fwd_ws<kD>(N, M);
+      case DICP_WS_ODE_EXT_BWD: return ode_ext_bwd_ws<kD>(N, M);
+      case DICP_WS_ODE_SELF_FWD_ROWS: return ode_self_fwd_rows_ws<kD>(M, N);
+      case DICP_WS_ODE_SELF_FWD_PHASED: return M <= 0 || M >= N ? 0 : euler_step_phase_ws<kD>(M, N);
+      case DICP_WS_ODE_SELF_BWD_PART: return ode_self_bwd_ws<kD>(M, N < 1 ? 1 : (int)N);
+      default: return 0;
     }
-    case DICP_WS_ODE_SELF_FWD: return D == 2 ? ode_self_fwd_ws<2>(M) : ode_self_fwd_ws<3>(M);
-    case DICP_WS_ODE_SELF_BWD:
-    {
-      size_t a = D == 2 ? ws_r<OpOdeSelfBwd<2>>(r_bwd(), M, M) : ws_r<OpOdeSelfBwd<3>>(r_bwd(), M, M);
-      size_t b = D == 2 ? ws_r<OpOdeSelfBwdEta<2>>(r_bwd(), M, M) : ws_r<OpOdeSelfBwdEta<3>>(r_bwd(), M, M);
-      size_t c = D == 2 ? ws_r<OpOdeSelfBwd2<2>>(r_bwd(), M, M) : ws_r<OpOdeSelfBwd2<3>>(r_bwd(), M, M);
-      a = a > b ? a : b;
-      a = a > c ? a : c;
-      const size_t d = sym_ws_bytes(M, 2 * D);  // SymBwd and SymBwdEta: W = 2D
-      return a > d ? a : d;
-    }
-    case DICP_WS_ODE_EXT_FWD: return D == 2 ? ode_ext_fwd_ws<2>(N, M) : ode_ext_fwd_ws<3>(N, M);
-    case DICP_WS_ODE_EXT_BWD: return D == 2 ? ode_ext_bwd_ws<2>(N, M) : ode_ext_bwd_ws<3>(N, M);
-    case DICP_WS_ODE_SELF_FWD_ROWS:
-      return D == 2 ? ode_self_fwd_rows_ws<2>(M, N) : ode_self_fwd_rows_ws<3>(M, N);
-    case DICP_WS_ODE_SELF_FWD_PHASED:
-      if (M <= 0 || M >= N) return 0;
-      return D == 2 ? euler_step_phase_ws<2>(M, N) : euler_step_phase_ws<3>(M, N);
-    case DICP_WS_ODE_SELF_BWD_PART: {
-      const int np = N < 1 ? 1 : (int)N;
-      return D == 2 ? ode_self_bwd_part_ws<2>(M, np) : ode_self_bwd_part_ws<3>(M, np);
-    }
-    default: return 0;
-  }
+  });
 }
 
+// Diagnostics: the column splits of the D = 3 ordered operators.
 int dicp_lddmm_splits(int kind, int64_t M, int64_t N) {
   switch (kind) {
     case DICP_WS_ODE_SELF_BWD:
-      if (g_bwd_alg == 1)
-        return r_bwd() == 1 ? rowred_splits<OpOdeSelfBwd2<3>, 1>(M, M)
-             : r_bwd() == 2 ? rowred_splits<OpOdeSelfBwd2<3>, 2>(M, M)
-                            : rowred_splits<OpOdeSelfBwd2<3>, 4>(M, M);
-      return r_bwd() == 1 ? rowred_splits<OpOdeSelfBwd<3>, 1>(M, M)
-           : r_bwd() == 2 ? rowred_splits<OpOdeSelfBwd<3>, 2>(M, M)
-                          : rowred_splits<OpOdeSelfBwd<3>, 4>(M, M);
+      return visit_bwd_ord<3>(false, g_bwd_alg, [&](auto t) {
+        return for_rows(r_bwd(), [&](auto r) { return rowred_splits<op_of<decltype(t)>, decltype(r)::value>(M, M); });
+      });
     case DICP_WS_ODE_SELF_FWD:
-      return r_fwd() == 1 ? rowred_splits<OpOdeSelfFwd<3, false, true>, 1>(M, M)
-           : r_fwd() == 2 ? rowred_splits<OpOdeSelfFwd<3, false, true>, 2>(M, M)
-                          : rowred_splits<OpOdeSelfFwd<3, false, true>, 4>(M, M);
+      return for_rows(r_fwd(), [&](auto r) {
+        return rowred_splits<OpOdeSelfFwd<3, false, true>, decltype(r)::value>(M, M);
+      });
     default: return rowred_splits<OpKRed<3>, kR>(M, N);
   }
 }

@@ -447,9 +447,10 @@ const char* dicp_version(void);
 /* 1 if D is compiled in. */
 int dicp_supports_dim(int D);
 /* Tuning / A-B knobs (process-wide unless stated; results of every setting agree to fp32
- * summation order):
- *   "fwd_alg"      eta = 0 ODE forward: 0 ordered rows, 1 symmetric pair-once, 2 packed-FP32
- *                  (default: ordered packed rows, and for whole passes from 20k points -- or,
+ * summation order).  One line per option of the library's table (csrc/lddmm.hip kOptions),
+ * in its order, with the default:
+ *   "fwd_alg"      (default 2) eta = 0 ODE forward: 0 ordered rows, 1 symmetric pair-once, 2
+ *                  packed-FP32 (ordered packed rows, and for whole passes from 20k points -- or,
  *                  under a "batch_share" hint, >= 1e9 pairs over the sharing calls -- the
  *                  symmetric pass of 5; its mG-less form stays ordered), 3 channel
  *                  contraction on the matrix cores (opt-in; fp32 error bounded by the rows'
@@ -458,57 +459,63 @@ int dicp_supports_dim(int D);
  *                  sums wherever it applies (whole passes in scaled coordinates; row slices and
  *                  raw coordinates run the ordered rows), 6 ordered packed rows always;
  *                  eta != 0: >= 2 packed-FP32 rows, otherwise ordered scalar rows
- *   "bwd_alg"      eta = 0 VJP: 0 / 1 ordered pair algebras, 2 symmetric pair-once, 3 symmetric
- *                  with packed-FP32 rows (default)
- *   "bwd_eta_alg"  eta != 0 VJP: 0 ordered, 1 symmetric, 2 symmetric packed-FP32 (default)
- *   "r_fwd" / "r_bwd"  rows per thread {1,2,4} of the ordered passes (env DICP_R_FWD / DICP_R_BWD)
- *   "split_rounds", "force_splits", "sym_L"  column-split / symmetric-chunk geometry (0 = auto)
- *   "min_chunk"    smallest column chunk of a split, 16..65536; 0 (default) = 256
- *   "pk_rp"        packed row passes: row pairs per thread, 0 automatic (2 for the eta = 0 fused
- *                  forward and the packed external-point / KRed passes from 32k rows and 8k
- *                  columns, else 1), 1 or 2 forced
- *   "sym_rp"       packed symmetric eta = 0 VJP: row pairs per lane, 0 automatic (2, i.e. 4 rows
- *                  in 256-point groups, for whole passes from 40k points, for row-split parts
- *                  from 64k points with >= 2e9 pairs per part, under a "batch_share" hint from
- *                  1e9 pairs over the sharing calls; else 1), 1 or 2 forced
- *   "red_alg"      KBase / KRedScal / KRed / GradKRed and the external-point forward: 0 never
- *                  the centred expansion, 1 automatic by size (default), 2 always
- *   "sym_red"      KBase / KRedScal / KRed with the rows equal to the columns (x == y): 0 never
- *                  the pair-once symmetric centred sum, 1 automatic (default: wherever the
- *                  centred expansion applies -- "red_alg" -- i.e. from 50k x 50k), 2 always
+ *   "bwd_alg"      (default 3) eta = 0 VJP: 0 / 1 ordered pair algebras, 2 symmetric pair-once,
+ *                  3 symmetric with packed-FP32 rows
+ *   "bwd_eta_alg"  (default 2) eta != 0 VJP: 0 ordered, 1 symmetric, 2 symmetric packed-FP32
+ *   "r_fwd"        (default 2; env DICP_R_FWD) rows per thread {1, 2, 4} of the ordered forward
+ *   "r_bwd"        (default 1; env DICP_R_BWD) rows per thread {1, 2, 4} of the ordered VJP
+ *   "split_rounds" (default 0 = automatic) column-split rounds, 0 .. 64
+ *   "force_splits" (default 0 = automatic) column splits of every split pass, 0 .. 65536
+ *   "sym_L"        (default 0 = automatic) column groups per workgroup of the symmetric passes,
+ *                  0 .. 64
+ *   "min_chunk"    (default 0 = 256) smallest column chunk of a split, 16 .. 65536
+ *   "pk_rp"        (default 0) packed row passes: row pairs per thread, 0 automatic (2 for the
+ *                  eta = 0 fused forward and the packed external-point / KRed passes from 32k
+ *                  rows and 8k columns, else 1), 1 or 2 forced
+ *   "sym_rp"       (default 0) packed symmetric eta = 0 VJP: row pairs per lane, 0 automatic (2,
+ *                  i.e. 4 rows in 256-point groups, for whole passes from 40k points, for
+ *                  row-split parts from 64k points with >= 2e9 pairs per part, under a
+ *                  "batch_share" hint from 1e9 pairs over the sharing calls; else 1), 1 or 2 forced
+ *   "red_alg"      (default 1) KBase / KRedScal / KRed / GradKRed and the external-point forward:
+ *                  0 never the centred expansion, 1 automatic by size, 2 always
+ *   "sym_red"      (default 1) KBase / KRedScal / KRed with the rows equal to the columns
+ *                  (x == y): 0 never the pair-once symmetric centred sum, 1 automatic (wherever
+ *                  the centred expansion applies -- "red_alg" -- i.e. from 50k x 50k), 2 always
  *                  (x == y only)
- *   "sym_red_rows" rows per lane of the pair-once sums: 0 automatic (4), 4 or 8 forced
- *   "sym_fwd_rows" rows per lane of the symmetric eta = 0 forward: 0 automatic (6 from 40k, 8 from 180k
- *                  points alone on the chip, else 4), 4, 6 or 8 forced
- *   "pair_cutoff"  Gaussian cutoff of far tile pairs in the symmetric shooting kernels: 0 off, 1
- *                  automatic (default: dense Euler self-shootings at eta = 0 from 32768 points run in
- *                  spatial order with boxes), 2 at every size
- *   "pair_cutoff_log2"  T of the cutoff: tile pairs whose every K is below 2^-T are skipped
- *                  (default 48, 8 .. 150)
- *   "lse_pk"       GMM E / M passes: 1 rows packed in float2 pairs (v_pk_fma_f32, default),
+ *   "sym_red_rows" (default 0) rows per lane of the pair-once sums: 0 automatic (4), 4 or 8 forced
+ *   "sym_fwd_rows" (default 0) rows per lane of the symmetric eta = 0 forward: 0 automatic (6 from
+ *                  40k, 8 from 180k points alone on the chip, else 4), 4, 6 or 8 forced
+ *   "pair_cutoff"  (default 1) Gaussian cutoff of far tile pairs in the symmetric shooting
+ *                  kernels: 0 off, 1 automatic (dense Euler self-shootings at eta = 0 from 32768
+ *                  points run in spatial order with boxes), 2 at every size
+ *   "pair_cutoff_log2"  (default 48) T of the cutoff, 8 .. 150: tile pairs whose every K is
+ *                  below 2^-T are skipped
+ *   "lse_pk"       (default 1) GMM E / M passes: 1 rows packed in float2 pairs (v_pk_fma_f32),
  *                  0 scalar rows (bitwise equal)
- *   "lse_adapt"    GMM E / M passes: tiles with a tile-end re-reference (anywhere in the
- *                  workgroup) before the rest of the chunk tests per pair; 0 per pair from the
- *                  start (default 1; env DICP_LSE_ADAPT)
- *   "lse_bound"    hinted GMM E-step against >= 8192 components: 1 (default; env
- *                  DICP_LSE_BOUND) the shift min(hint - 8, max_c w2_c - 8), which no logit can
- *                  overflow, and rows whose LSE ends > 80 below it summed again exactly; 0 the
- *                  sampled shift (unhinted calls always take the sampled shift)
- *   "cx_rho_x100"  centred expansion: largest compact sub-tile radius (scaled units x 100)
- *   "mfma_rmax_x100"  matrix-core forward (fwd_alg 3): largest workgroup row spread (scaled
- *                  units x 100) that takes the MFMA branch; >= 100000 always, 0 never (default 300)
- *   "ext_alg"      KRed and the external-point passes below the centred sizes: 0 generic
- *                  scalar rows, 1 packed-FP32 rows (default)
- *   "batch_share"  PER HOST THREAD geometry hint, default 1: the number of equal calls a launch
- *                  shares the device with (the frames of a launch batch); split counts, column
- *                  groups per workgroup and the 4-row rules are then sized for 1/share of the
- *                  chip.  Changes only the fp32 summation order; a call made alone with the same
- *                  share computes the same bits.  Workspace sizes do not depend on it.
- *   "coord_raw"    PER HOST THREAD: 1 runs the default packed shooting kernels (fwd_alg 2,
- *                  bwd_alg 3) in original-unit coordinates -- exact pair differences at any
- *                  cloud extent, one packed multiply more per two pairs; 0 (default) scaled
+ *   "lse_adapt"    (default 1; env DICP_LSE_ADAPT) GMM E / M passes: tiles with a tile-end
+ *                  re-reference (anywhere in the workgroup) before the rest of the chunk tests
+ *                  per pair; 0 per pair from the start
+ *   "lse_bound"    (default 1; env DICP_LSE_BOUND) hinted GMM E-step against >= 8192 components:
+ *                  1 the shift min(hint - 8, max_c w2_c - 8), which no logit can overflow, and
+ *                  rows whose LSE ends > 80 below it summed again exactly; 0 the sampled shift
+ *                  (unhinted calls always take the sampled shift)
+ *   "cx_rho_x100"  (default 150) centred expansion: largest compact sub-tile radius (scaled
+ *                  units x 100), 0 .. 100000
+ *   "mfma_rmax_x100"  (default 300) matrix-core forward (fwd_alg 3): largest workgroup row spread
+ *                  (scaled units x 100) that takes the MFMA branch; >= 100000 always, 0 never
+ *   "ext_alg"      (default 1) KRed and the external-point passes below the centred sizes: 0
+ *                  generic scalar rows, 1 packed-FP32 rows
+ *   "batch_share"  (default 1) PER HOST THREAD geometry hint, 1 .. 4096: the number of equal calls
+ *                  a launch shares the device with (the frames of a launch batch); split counts,
+ *                  column groups per workgroup and the 4-row rules are then sized for 1/share of
+ *                  the chip.  Changes only the fp32 summation order; a call made alone with the
+ *                  same share computes the same bits.  Workspace sizes do not depend on it.
+ *   "coord_raw"    (default 0) PER HOST THREAD: 1 runs the default packed shooting kernels
+ *                  (fwd_alg 2, bwd_alg 3) in original-unit coordinates -- exact pair differences
+ *                  at any cloud extent, one packed multiply more per two pairs; 0 scaled
  *                  coordinates alpha (q - q_0), float32-exact up to ~200 sigma of extent
- * Returns DICP_ERR_INVALID for an unknown name or an out-of-range value. */
+ * Returns DICP_ERR_INVALID for an unknown or NULL name (with a message) or an out-of-range
+ * value (the stored value is then unchanged). */
 int dicp_set_option(const char* name, int value);
 /* Current value of a knob of dicp_set_option (same names; the compile-time defaults until
  * set), written to *value.  Returns DICP_ERR_INVALID for an unknown name or a NULL value.
