@@ -24,7 +24,7 @@ KBASE, KREDSCAL, KRED, GRADK, GRADK_REV, DDK, GENDK, HESSK, LAPK, GRADLAPK, GRAD
 # enum dicp_ws_kind
 WS_RED, WS_ODE_SELF_FWD, WS_ODE_SELF_BWD, WS_ODE_EXT_FWD, WS_ODE_EXT_BWD, WS_GMM_ESTEP, \
     WS_GMM_MSTEP, WS_GMM_TARGETS, WS_RIDGE_CG, WS_ODE_SELF_FWD_ROWS, WS_ODE_SELF_BWD_PART, WS_GRAD, \
-    WS_ODE_SELF_FWD_PHASED, WS_GMM_ASSIGN, WS_ODE_EXT_JAC = range(15)
+    WS_ODE_SELF_FWD_PHASED, WS_GMM_ASSIGN, WS_ODE_EXT_JAC, WS_ODE_EXT_INV = range(16)
 # enum dicp_grad_kind
 GRAD_HESSW, GRAD_HESSWP, GRAD_ZDOTV, GRAD_HESS3, GRAD_GRADLAP3 = range(5)
 
@@ -50,6 +50,8 @@ _SIGNATURES = {
                                    _P, _SZ, _P],
     "dicp_lddmm_ode_ext_jac_f32": [_P, _I64, _P, _P, _I64, _INT, _DBL, _DBL, _P, _P, _P, _SZ, _P],
     "dicp_lddmm_ext_jac_step_f32": [_P, _P, _I64, _P, _P, _I64, _INT, _DBL, _DBL, _DBL, _P, _P, _P, _SZ, _P],
+    "dicp_lddmm_ext_inv_step_f32": [_P, _P, _P, _P, _I64, _P, _P, _I64, _INT, _DBL, _DBL, _DBL, _P, _P, _P, _SZ,
+                                    _P],
     "dicp_gmm_estep_f32": [_P, _I64, _P, _P, _P, _I64, _INT, _DBL, _DBL, _P, _P, _P, _P, _SZ, _P],
     "dicp_gmm_estep_hint_f32": [_P, _I64, _P, _P, _P, _I64, _INT, _DBL, _DBL, _P, _P, _P, _P, _P, _SZ, _P],
     "dicp_gmm_mstep_f32": [_P, _P, _I64, _P, _P, _I64, _INT, _DBL, _P, _P, _SZ, _P],
@@ -830,6 +832,40 @@ def ext_jac_step(x, G, q, p, sigma: float, eta: float, dt: float):
                                                            _ptr(Gn), _ptr(ws), nb, _stream(x.device)))
     _check_rc(rc, "ext_jac_step")
     return xn, Gn
+
+
+def ext_inv_step(x, y, q, p, sigma: float, eta: float, dt: float, v1=None, A1=None):
+    """One Newton update towards F(x) = y of a step map of the carried points' discrete flow
+    (dicp_lddmm_ext_inv_step_f32): returns (x_next (N, D), res (N,)), res the residual
+    |F(x) - y|_inf of the INPUT x.  v1 = A1 = None: the Euler step at (x; q, p); otherwise the
+    Ralston step, (v1, A1) = ode_ext_jac(x, q_t, p_t) and (q, p) the mid-state.  A row with a
+    singular DF or non-finite inputs is NaN in both outputs."""
+    x, q, p = _jac_args(x, q, p, "ext_inv_step")
+    y = _dev(y, "y")
+    N, D = x.shape
+    M = q.shape[0]
+    if y.shape != x.shape:
+        raise ValueError(f"ext_inv_step: y must be shaped {tuple(x.shape)}, got {tuple(y.shape)}")
+    if (v1 is None) != (A1 is None):
+        raise ValueError("ext_inv_step: v1 and A1 go together")
+    if v1 is not None:
+        v1 = _dev(v1, "v1")
+        A1 = _dev(A1, "A1")
+        if v1.shape != (N, D) or A1.shape != (N, D, D):
+            raise ValueError(f"ext_inv_step: v1 ({N}, {D}) and A1 ({N}, {D}, {D}) expected")
+    xn = torch.empty_like(x)
+    res = torch.empty(N, device=x.device, dtype=torch.float32)
+    if N == 0:
+        return xn, res
+    ws, nb = _workspace(WS_ODE_EXT_INV, M, N, D, x.device)
+    # the same pair operator as ode_ext_jac, accounted under its name
+    rc = _launch("ode_ext_jac", N * M, 4 * (N * (3 * D + 1 + (0 if v1 is None else D + D * D)) + 2 * M * D),
+                 lambda: lib().dicp_lddmm_ext_inv_step_f32(_ptr(x), _ptr(y), _ptr(v1), _ptr(A1), N, _ptr(q),
+                                                           _ptr(p), M, D, float(sigma), float(eta), float(dt),
+                                                           _ptr(xn), _ptr(res), _ptr(ws), nb,
+                                                           _stream(x.device)))
+    _check_rc(rc, "ext_inv_step")
+    return xn, res
 
 
 def ode_ext_bwd(x, q, p, gvx, gdiv, sigma: float, eta: float, gq, gp):

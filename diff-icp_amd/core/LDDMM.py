@@ -13,6 +13,7 @@ from __future__ import annotations
 import math
 import os
 import threading
+import warnings
 import weakref
 
 import torch
@@ -434,6 +435,78 @@ class LDDMMModel:
                     G = G + (dt / 4) * B1 + (3 * dt / 4) * B2
             J = G + torch.eye(D, device=x.device, dtype=x.dtype)
         return x, J
+
+    def flow_inverse(self, q0, p0, y1, shoot=None, tol=None, max_iter=10):
+        """x0 with phi(x0) = y1 for the DISCRETE flow phi that Shoot(q0, p0, x0) / flow_jacobian
+        compute: the exact inverse of that map (up to tol), not the shooting from (q1, -p1) of the
+        reference's `backward`, which inverts only the continuous flow of the eta = 0 field.
+        For t = nt-1 ... 0 Newton's iteration solves F_t(x_t) = x_{t+1} from x_t = x_{t+1}, F_t the
+        step map of the scheme (_lib.ext_inv_step: v and A = dv/dx in one pair pass, a D x D solve
+        per row; Ralston: the first stage's (v1, A1) from _lib.ode_ext_jac, the mid-states formed
+        once per time step as in flow_jacobian).  Every pass returns the residual |F_t(x) - x_{t+1}|_inf
+        of its INPUT x; a step stops, keeping that input, once the largest finite residual is <= tol
+        or after max_iter updates (k updates cost k + 1 passes, one host read each).  Rows whose
+        residual is not finite (NaN input, singular DF) take no part in the stopping test.
+        tol: coordinate units; None: 1e-6 max(sigma, max finite |y1|).
+        shoot: a forward shoot of (q0, p0) whose support states are reused (its final momenta are
+        never read: a shoot with p1_missing stays as it is); None: they are computed here.
+        Returns (x0, info): rows that did not converge are NaN in x0 (one RuntimeWarning counts
+        them); info = dict(converged (N,) bool, residual (N,) float32: the largest certified
+        residual over the steps, iterations: the nt update counts (entry t: step t), passes: the
+        pair passes of the velocity-gradient operator made, tol).  Inputs are detached; the model
+        (its shoot_cache included) is left as it was.  Single device."""
+        getspec(q0, p0, y1)
+        q0, p0, y1 = q0.detach(), p0.detach(), y1.detach()
+        if shoot is None:
+            Q, P = self._support_states(q0, p0, need_p1=False)
+        else:
+            Q, P = shoot.Q.detach(), shoot.P.detach()
+        nt = Q.shape[0] - 1
+        sigma, eta, dt = self.Kernel.sigma, float(self.eta), 1.0 / nt
+        euler = self.scheme == "Euler"
+        y = y1.contiguous()
+        N = y.shape[0]
+        raw = self._raw_for(q0)
+        nan = float("nan")
+        with torch.no_grad():
+            if tol is None:
+                a = y.abs()
+                big = float(torch.where(torch.isfinite(a), a, torch.zeros_like(a)).max()) if y.numel() else 0.0
+                tol = 1e-6 * max(float(sigma), big)
+            tol = float(tol)
+            worst = torch.zeros(N, device=y.device, dtype=y.dtype)
+            iterations = [0] * nt
+            passes = 0
+            for t in range(nt - 1, -1, -1):
+                q, p = Q[t], P[t]
+                if not euler:
+                    with _lib.coord_mode(raw):
+                        vq, mG = _lib.ode_self_fwd(q, p, sigma, eta, False)[:2]
+                    qm, pm = q + (2 * dt / 3) * vq, p + (2 * dt / 3) * mG
+                x, k = y, 0
+                while True:
+                    if euler:
+                        xn, res = _lib.ext_inv_step(x, y, q, p, sigma, eta, dt)
+                        passes += 1
+                    else:
+                        v1, A1 = _lib.ode_ext_jac(x, q, p, sigma, eta)
+                        xn, res = _lib.ext_inv_step(x, y, qm, pm, sigma, eta, dt, v1, A1)
+                        passes += 2
+                    finite = torch.isfinite(res)
+                    rmax = float(torch.where(finite, res, torch.zeros_like(res)).max()) if N else 0.0
+                    if rmax <= tol or k >= max_iter:
+                        break
+                    x, k = xn, k + 1
+                iterations[t] = k
+                worst = torch.maximum(worst, res)          # NaN stays NaN
+                y = torch.where(finite[:, None], x, torch.full_like(x, nan))
+            converged = worst <= tol
+            x0 = torch.where(converged[:, None], y, torch.full_like(y, nan))
+        bad = N - int(converged.sum())
+        if bad:
+            warnings.warn(f"flow_inverse: {bad} of {N} points did not converge to tol = {tol:.3g} "
+                          f"within {max_iter} Newton updates per step (returned as NaN)", RuntimeWarning)
+        return x0, dict(converged=converged, residual=worst, iterations=iterations, passes=passes, tol=tol)
 
     def BasicQuadLossFunctor(self, y, cmul=1):
         y = y.detach()

@@ -149,6 +149,15 @@ class MultiPSR:
         index, log_resp = self.GMMi[s].nearest_points(X, k=topk)
         return index.to(dev), log_resp.to(**self.dataspec)
 
+    def transfer(self, X, k_from, k_to):
+        """The points X of frame k_from's data space carried into frame k_to's:
+        Registration(k_to).inverse(Registration(k_from).apply(X)) (no reference counterpart; rows
+        whose inverse does not converge are NaN, Registration.inverse).  Computed on the compute
+        spec, returned on the data spec; changes no state."""
+        with torch.no_grad():
+            Y = self.Registration(k_from).apply(X.detach().to(**self.compspec))
+            return self.Registration(k_to).inverse(Y).to(**self.dataspec)
+
     # ------------------------------------------------------------------------------------
     def _assign_targets(self, s, allys):
         last = 0
@@ -266,6 +275,15 @@ class DiffPSR(MultiPSR):
         # concurrency, decides the fp32 summation order)
         self.batch_share = 0
         self.initialize_a0()
+
+    def template_in_frame(self, k, s=0):
+        """The template centres GMMi[s].mu carried into frame k's data space by the inverse of
+        frame k's registration (no reference counterpart; NaN where the inverse does not
+        converge, Registration.inverse).  Computed on the compute spec, returned on the data
+        spec; changes no state."""
+        with torch.no_grad():
+            mu = self.GMMi[s].mu.detach().to(**self.compspec)
+            return self.Registration(k).inverse(mu).to(**self.dataspec)
 
     def initialize_a0(self, **v2p_args):
         """a0 giving zero initial speeds (PSR.py:406-413)."""

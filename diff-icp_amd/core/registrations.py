@@ -6,11 +6,31 @@ import torch
 from .LDDMM import LDDMMModel
 
 
+def _inv_small(J):
+    """Inverses of the (N, D, D) matrices J, D = 2 or 3, by cofactors (non-finite where singular)."""
+    D = J.shape[-1]
+    if D == 2:
+        a, b, c, d = J[:, 0, 0], J[:, 0, 1], J[:, 1, 0], J[:, 1, 1]
+        adj = torch.stack([d, -b, -c, a], 1).reshape(-1, 2, 2)
+        return adj / (a * d - b * c)[:, None, None]
+    if D != 3:
+        return torch.linalg.inv(J)
+    r0, r1, r2 = J[:, 0], J[:, 1], J[:, 2]
+    c0, c1, c2 = torch.linalg.cross(r1, r2), torch.linalg.cross(r2, r0), torch.linalg.cross(r0, r1)
+    det = (r0 * c0).sum(-1)
+    return torch.stack([c0, c1, c2], 2) / det[:, None, None]
+
+
 class Registration:
     def apply(self, X: torch.Tensor):
         pass
 
     def backward(self, Y: torch.Tensor):
+        """The reference's backward map; not the inverse of apply() (that is inverse())."""
+        pass
+
+    def inverse(self, Y: torch.Tensor):
+        """X with apply(X) = Y."""
         pass
 
     def shoot(self, X: torch.Tensor, backward=False):
@@ -41,7 +61,31 @@ class LDDMMRegistration(Registration):
         return self.shoot(X)[-1][3]
 
     def backward(self, Y, previous_forwardshoot=None):
+        """The reference's backward map: the shooting of Y from (q1, -a1) (registrations.py:80-87).
+        It is NOT the inverse of the map apply() computes: it inverts the continuous flow only,
+        and only where the field is odd in the momenta (eta = 0).  The inverse is inverse()."""
         return self.shoot(Y, backward=True, previous_forwardshoot=previous_forwardshoot)[-1][3]
+
+    # ------------------------------------------------------------------------------------
+    # Exact inverse of the map apply() computes (extension; LDDMMModel.flow_inverse)
+    def inverse(self, Y, previous_forwardshoot=None, tol=None, max_iter=10, return_info=False):
+        """X with apply(X) = Y: the inverse of the discrete flow itself, by Newton's iteration on
+        every step map (LDDMMModel.flow_inverse; tol in coordinate units, None: 1e-6 of the
+        larger of sigma and max |Y|).  Rows that do not converge within max_iter updates per
+        step are NaN (one RuntimeWarning).  previous_forwardshoot: a forward shoot of (q0, a0)
+        to reuse.  return_info: (X, info), info as flow_inverse returns it.  Y is detached;
+        nothing of the model changes."""
+        X, info = self.LMi.flow_inverse(self.q0, self.a0, Y, shoot=previous_forwardshoot, tol=tol,
+                                        max_iter=max_iter)
+        return (X, info) if return_info else X
+
+    def inverse_with_jacobian(self, Y):
+        """(X, Jinv): X = inverse(Y) and Jinv[i] = d X_i / d Y_i, the inverse of jacobian(X)[i]
+        (formed in float64, returned as float32); NaN where X is NaN."""
+        X = self.inverse(Y)
+        Jinv = _inv_small(self.jacobian(X).double()).to(X.dtype)     # NaN rows of X: NaN rows of J
+        bad = torch.isnan(X).any(dim=1)
+        return X, torch.where(bad[:, None, None], torch.full_like(Jinv, float("nan")), Jinv)
 
     # ------------------------------------------------------------------------------------
     # Local behaviour of the map (extension; LDDMMModel.flow_jacobian)

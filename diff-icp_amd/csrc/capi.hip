@@ -17,6 +17,7 @@ size_t dicp_assign_ws(int64_t M, int64_t N, int D);
 int dicp_assign_splits(int64_t M, int64_t N);
 size_t dicp_ext_jac_ws(int64_t M, int64_t N, int D);
 int dicp_ext_jac_splits(int64_t M, int64_t N);
+size_t dicp_ext_inv_ws(int64_t M, int64_t N, int D);
 
 namespace {
 thread_local char g_err[512] = "";
@@ -56,6 +57,8 @@ extern "C" size_t dicp_workspace_bytes(int kind, int64_t M, int64_t N, int D) {
     b = dicp_assign_ws(M, N, D);
   else if (kind == DICP_WS_ODE_EXT_JAC)
     b = dicp_ext_jac_ws(M, N, D);
+  else if (kind == DICP_WS_ODE_EXT_INV)
+    b = dicp_ext_inv_ws(M, N, D);
   else if (kind == DICP_WS_RIDGE_CG)
     b = dicp_solve_ws(kind, M, D);
   else if (kind >= DICP_WS_GMM_ESTEP && kind <= DICP_WS_GMM_TARGETS)
@@ -68,7 +71,8 @@ extern "C" size_t dicp_workspace_bytes(int kind, int64_t M, int64_t N, int D) {
 
 extern "C" int dicp_num_splits(int kind, int64_t M, int64_t N) {
   if (kind == DICP_WS_GMM_ASSIGN) return dicp_assign_splits(M, N);
-  if (kind == DICP_WS_ODE_EXT_JAC) return dicp_ext_jac_splits(M, N);
+  // the Newton step's pair pass is the velocity-gradient pass itself
+  if (kind == DICP_WS_ODE_EXT_JAC || kind == DICP_WS_ODE_EXT_INV) return dicp_ext_jac_splits(M, N);
   return dicp_lddmm_splits(kind, M, N);
 }
 

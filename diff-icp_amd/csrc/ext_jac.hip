@@ -18,6 +18,10 @@
 // is the same pass: the row's product A (I + G) is formed where the row is stored (linear in
 // the sums as well, so it too passes through the slabs) and base + dt * value is the
 // skeleton's output epilogue, in the kernel or in the merge.
+//
+// The Newton update towards F(x) = y of a step map F of that flow (the exact inverse of the
+// discrete flow, LDDMMModel.flow_inverse) needs the same (v, A) but is not linear in them: the
+// pass writes them to a scratch region and a row-wise kernel solves the D x D system (below).
 #include "launch.hpp"
 #include "lddmm_ops.hpp"
 #include "packed.hpp"
@@ -200,6 +204,126 @@ int hip_rc(const char* name, hipError_t e) {
   return DICP_ERR_HIP;
 }
 
+
+// ---- Newton update of one step map of the discrete flow (dicp_lddmm_ext_inv_step_f32) ----
+// The update x+ = x - DF^-1 r is not linear in the pair sums, so it cannot pass through the
+// partial slabs as an output: (v | A) of the pass go, through the slabs where the pass is split,
+// into a scratch region at the head of the workspace, and a row-wise kernel applies the update.
+
+// mid-point of the Ralston step: xm = x + h v1 (the rows of the second stage's pair pass)
+__global__ __launch_bounds__(kBlock) void inv_mid_kernel(const float* __restrict__ x, const float* __restrict__ v1,
+                                                         float h, int64_t n, float* __restrict__ xm) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (e < n) xm[e] = fmaf(h, v1[e], x[e]);
+}
+
+// One thread per row.  va: (v (N, D) | A (N, D, D)) of the pass, or NULL (no support: zero).
+// v1 == NULL: Euler, F = x + dt v, DF = I + dt A; otherwise Ralston with (v, A) = (v2, A2):
+// F = x + dt/4 v1 + 3 dt/4 v2, DF = I + dt/4 A1 + 3 dt/4 A2 (I + h A1), h = 2 dt / 3.
+// r = (x - y) + (F - x); the D x D solve by cofactors, every index a compile-time constant.
+template <int D>
+__global__ __launch_bounds__(kBlock) void inv_update_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                            const float* __restrict__ v1,
+                                                            const float* __restrict__ A1,
+                                                            const float* __restrict__ va, int64_t N, float dt,
+                                                            float* __restrict__ xn, float* __restrict__ res) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= N) return;
+  float xi[D], yi[D], v[D], A[D * D], r[D], m[D * D];
+  ld<D>(x, i, xi);
+  ld<D>(y, i, yi);
+  if (va != nullptr) {
+    ld<D>(va, i, v);
+    ld<D * D>(va + N * D, i, A);
+  } else {
+#pragma unroll
+    for (int d = 0; d < D; ++d) v[d] = 0.f;
+#pragma unroll
+    for (int e = 0; e < D * D; ++e) A[e] = 0.f;
+  }
+  if (v1 == nullptr) {
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      r[d] = fmaf(dt, v[d], xi[d] - yi[d]);
+#pragma unroll
+      for (int a = 0; a < D; ++a) m[d * D + a] = fmaf(dt, A[d * D + a], d == a ? 1.f : 0.f);
+    }
+  } else {
+    float w[D], B[D * D];
+    ld<D>(v1, i, w);
+    ld<D * D>(A1, i, B);
+    const float h = dt * (2.f / 3.f), c1 = 0.25f * dt, c2 = 0.75f * dt;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      r[d] = (xi[d] - yi[d]) + fmaf(c2, v[d], c1 * w[d]);
+#pragma unroll
+      for (int a = 0; a < D; ++a) {
+        float t = A[d * D + a];   // A2 (I + h A1)
+#pragma unroll
+        for (int c = 0; c < D; ++c) t = fmaf(h * A[d * D + c], B[c * D + a], t);
+        m[d * D + a] = fmaf(c2, t, fmaf(c1, B[d * D + a], d == a ? 1.f : 0.f));
+      }
+    }
+  }
+  float dx[D];
+  if constexpr (D == 2) {
+    const float det = m[0] * m[3] - m[1] * m[2];
+    dx[0] = (m[3] * r[0] - m[1] * r[1]) / det;
+    dx[1] = (m[0] * r[1] - m[2] * r[0]) / det;
+  } else {
+    const float c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
+    const float c10 = m[2] * m[7] - m[1] * m[8], c11 = m[0] * m[8] - m[2] * m[6], c12 = m[1] * m[6] - m[0] * m[7];
+    const float c20 = m[1] * m[5] - m[2] * m[4], c21 = m[2] * m[3] - m[0] * m[5], c22 = m[0] * m[4] - m[1] * m[3];
+    const float det = m[0] * c00 + m[1] * c01 + m[2] * c02;
+    dx[0] = (c00 * r[0] + c10 * r[1] + c20 * r[2]) / det;   // adj = cofactors transposed
+    dx[1] = (c01 * r[0] + c11 * r[1] + c21 * r[2]) / det;
+    dx[2] = (c02 * r[0] + c12 * r[1] + c22 * r[2]) / det;
+  }
+  float o[D], rm = 0.f, chk = 0.f;
+#pragma unroll
+  for (int d = 0; d < D; ++d) {
+    // no support, Euler: F is the identity and the solution is y itself
+    o[d] = (va == nullptr && v1 == nullptr) ? yi[d] : xi[d] - dx[d];
+    rm = fmaxf(rm, fabsf(r[d]));
+    chk += o[d] + r[d];
+  }
+  // singular DF (det = 0: x / 0) or a non-finite input: the whole row, and only it, is marked
+  const bool bad = !(fabsf(chk) <= 3.0e38f);
+  const float nan = __builtin_nanf("");
+#pragma unroll
+  for (int d = 0; d < D; ++d) xn[i * D + d] = bad ? nan : o[d];
+  res[i] = bad ? nan : rm;
+}
+
+template <int D>
+int ext_inv_d(const char* name, const float* x, const float* y, const float* v1, const float* A1, int64_t N,
+              const float* q, const float* p, int64_t M, double sigma, double eta, double dt, float* xn,
+              float* res, void* ws, size_t wsb, hipStream_t st) {
+  const size_t scratch = (size_t)N * (D + D * D) * sizeof(float);
+  float* va = nullptr;
+  if (M > 0) {
+    if (ws == nullptr || wsb < scratch) {
+      set_error("%s: workspace too small (%zu < %zu bytes)", name, wsb, scratch);
+      return DICP_ERR_WORKSPACE;
+    }
+    va = reinterpret_cast<float*>(ws);
+    const float* rows = x;
+    if (v1 != nullptr) {   // x_next holds the mid-point until the update overwrites it
+      const int64_t n = N * D;
+      inv_mid_kernel<<<dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st>>>(
+          x, v1, (float)(2.0 * dt / 3.0), n, xn);
+      if (int rc = check_launch(name)) return rc;
+      rows = xn;
+    }
+    if (int rc = ext_jac_d<D>("ext_inv_step", rows, nullptr, N, q, p, M, sigma, eta, false, 0.0, va, va + N * D,
+                              reinterpret_cast<char*>(ws) + scratch, wsb - scratch, st))
+      return rc;
+  }
+  inv_update_kernel<D><<<dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, st>>>(
+      x, y, v1, A1, va, N, (float)dt, xn, res);
+  return check_launch(name);
+}
+
 }  // namespace
 
 extern "C" int dicp_lddmm_ode_ext_jac_f32(const float* x, int64_t N, const float* q, const float* p, int64_t M,
@@ -262,4 +386,38 @@ size_t dicp_ext_jac_ws(int64_t M, int64_t N, int D) {
   const int S = dicp_ext_jac_splits(M, N);
   if (S <= 1) return 0;
   return (size_t)S * (size_t)N * (size_t)(D + D * D) * sizeof(float);
+}
+
+extern "C" int dicp_lddmm_ext_inv_step_f32(const float* x, const float* y, const float* v1, const float* A1,
+                                           int64_t N, const float* q, const float* p, int64_t M, int D,
+                                           double sigma, double eta, double dt, float* x_next, float* res,
+                                           void* ws, size_t ws_bytes, dicp_stream_t stream) {
+  const char* name = "dicp_lddmm_ext_inv_step_f32";
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  bool done;
+  if (int rc = jac_check(name, x, N, q, p, M, D, sigma, x_next, &done)) return rc;
+  if ((v1 == nullptr) != (A1 == nullptr)) {
+    set_error("%s: invalid arguments (v1 and A1 go together)", name);
+    return DICP_ERR_INVALID;
+  }
+  if (done) return DICP_OK;
+  if (!y || !res) {
+    set_error("%s: invalid arguments (NULL pointer)", name);
+    return DICP_ERR_INVALID;
+  }
+  if (x_next == x || x_next == y || x_next == v1) {
+    set_error("%s: invalid arguments (outputs must not alias inputs)", name);
+    return DICP_ERR_INVALID;
+  }
+  if (int rc = no_batch("ext_inv_step")) return rc;
+  return D == 2 ? ext_inv_d<2>(name, x, y, v1, A1, N, q, p, M, sigma, eta, dt, x_next, res, ws, ws_bytes, st)
+                : ext_inv_d<3>(name, x, y, v1, A1, N, q, p, M, sigma, eta, dt, x_next, res, ws, ws_bytes, st);
+}
+
+// dicp_workspace_bytes(DICP_WS_ODE_EXT_INV, M, N, D): the (v | A) scratch of N rows at the head,
+// then the partial slabs of DICP_WS_ODE_EXT_JAC (in its 256-byte granule)
+size_t dicp_ext_inv_ws(int64_t M, int64_t N, int D) {
+  if ((D != 2 && D != 3) || M <= 0 || N <= 0) return 0;
+  const size_t slabs = (dicp_ext_jac_ws(M, N, D) + 255) / 256 * 256;
+  return (size_t)N * (size_t)(D + D * D) * sizeof(float) + slabs;
 }

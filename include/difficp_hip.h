@@ -159,6 +159,24 @@ int dicp_lddmm_ext_jac_step_f32(const float* x, const float* G, int64_t N, const
                                 double dt, float* x_next, float* G_next, void* ws,
                                 size_t ws_bytes, dicp_stream_t stream);
 
+/* One Newton update towards F(x) = y of a step map F of the discrete flow of the carried points
+ * (no reference counterpart), x_next = x - DF(x)^-1 r with r = (x - y) + (F(x) - x), and
+ * res_i = |r_i|_inf, the residual of the INPUT x (N,).  (v, A) as in dicp_lddmm_ode_ext_jac_f32:
+ *   v1 == NULL (then A1 must be NULL): the Euler step, F = x + dt v(x; q, p), DF = I + dt A;
+ *   otherwise the Ralston second stage, h = 2 dt / 3: (v1, A1) are the first stage's, taken at
+ *   (x; q_t, p_t) by dicp_lddmm_ode_ext_jac_f32, and (v2, A2) are evaluated here at x + h v1
+ *   against (q, p), which the caller passes as the mid-state S_t + h ODE(S_t):
+ *     F = x + dt/4 v1 + 3 dt/4 v2,   DF = I + dt/4 A1 + 3 dt/4 A2 (I + h A1).
+ * One pair pass (the sums of the velocity gradient) and a row-wise D x D solve.  x_next must not
+ * alias x, y or v1.  A row whose DF is singular or whose inputs are not finite gets NaN in
+ * x_next and res; no other row is affected.  D = 2 or 3 (otherwise DICP_ERR_UNSUPPORTED).
+ * N = 0 launches nothing; M = 0 means v = A = 0 (Euler: x_next = y, res = |x - y|_inf).
+ * Deterministic (no atomics).  Workspace kind DICP_WS_ODE_EXT_INV. */
+int dicp_lddmm_ext_inv_step_f32(const float* x, const float* y, const float* v1, const float* A1,
+                                int64_t N, const float* q, const float* p, int64_t M, int D,
+                                double sigma, double eta, double dt, float* x_next, float* res,
+                                void* ws, size_t ws_bytes, dicp_stream_t stream);
+
 /* VJP of the external-point terms.  Cotangents gvx (N,D) on vx and device scalar gdiv on
  * sum_i gx_i.  Writes gxo (N,D) (gradient w.r.t. x) and ACCUMULATES into gq, gp (M,D)
  * (gradient w.r.t. the support points / momenta), so it can follow the self backward. */
@@ -437,8 +455,10 @@ enum dicp_ws_kind {
   DICP_WS_GRAD = 11,             /* dicp_gauss_red_grad_f32: M rows, N columns */
   DICP_WS_ODE_SELF_FWD_PHASED = 12, /* dicp_lddmm_euler_step_phase_f32: M = rows, N = points */
   DICP_WS_GMM_ASSIGN = 13,       /* dicp_gmm_assign_f32: M = rows, N = columns */
-  DICP_WS_ODE_EXT_JAC = 14       /* dicp_lddmm_ode_ext_jac_f32 / dicp_lddmm_ext_jac_step_f32: M = support
+  DICP_WS_ODE_EXT_JAC = 14,      /* dicp_lddmm_ode_ext_jac_f32 / dicp_lddmm_ext_jac_step_f32: M = support
                                     points, N = carried points (as DICP_WS_ODE_EXT_FWD) */
+  DICP_WS_ODE_EXT_INV = 15       /* dicp_lddmm_ext_inv_step_f32: M = support points, N = carried points;
+                                    the slabs of DICP_WS_ODE_EXT_JAC and N (D + D^2) floats of scratch */
 };
 size_t dicp_workspace_bytes(int kind, int64_t M, int64_t N, int D);
 
