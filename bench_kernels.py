@@ -31,6 +31,9 @@ FLOPS_PER_PAIR = {
     "GMM_TARGETS": 30,
     "GMM_ESTEP_NOSTATS": 12,  # 3 sub + 4 fma + the sum of the exps (+ 1 exp)
     "GMM_ASSIGN_K1": 13, "GMM_ASSIGN_K4": 13,   # 3 sub + mul + 3 fma, compare / select; no exp
+    # soft transfer (csrc/carry.hip): 3 sub + mul + 3 fma, the shift, the sum of the exps (+ 1 exp)
+    # and one fma per channel
+    "GMM_CARRY_F1": 14 + 2 * 1, "GMM_CARRY_F4": 14 + 2 * 4, "GMM_CARRY_F16": 14 + 2 * 16,
     "ODE_EXT_FWD": 22,        # v and the divergence row (eta = 0): 3 sub + mul + 7 fma
     "EXT_JAC": 35, "EXT_JAC_STEP": 35,   # v and the D x D gradient (eta = 0): 3 sub + 4 mul + 3 add + 12 fma
 }
@@ -158,6 +161,26 @@ def main():
         for K in (1, 4):
             t = timed(lambda: G.assign(X, k=K), reps=100)
             rep(f"API_ASSIGN_K{K}@{N}x{C}", t, N * C, 2 * nbytes + 8 * N * (K + 1))
+    if only is None or "CARRY" in only:
+        # the soft transfer next to its yardstick, the stats-less E-step at the same shape (the
+        # same pair count and one exp per pair), in the manner of ASSIGN: 100 back-to-back
+        # launches each, alternated three times; the 100k square, then the atlas shapes (carry:
+        # points x components; pool: components x points, which exercises the column split)
+        for (M, N, Fs) in [(n_big, n_big, (1, 4, 16)), (20000, 512, (1, 16)), (512, 640000, (1, 16))]:
+            rows = torch.rand(M, D, device=dev)
+            cols = torch.rand(N, D, device=dev)
+            bias = torch.randn(N, device=dev)
+            c2 = (cols * cols).sum(-1)
+            feats = {F: torch.randn(N, F, device=dev) for F in Fs}
+            nbytes = 4 * (4 * M + 4 * N)
+            for _ in range(3):
+                t = timed(lambda: _lib.gmm_estep(rows, cols, bias, c2, 0.05, 0.0, False), reps=100)
+                rep(f"GMM_ESTEP_NOSTATS@{M}x{N}", t, M * N, nbytes + 8 * M,
+                    {"splits": _lib.num_splits(_lib.WS_GMM_ESTEP, M, N)})
+                for F in Fs:
+                    t = timed(lambda: _lib.gmm_carry(rows, cols, bias, feats[F], 0.05), reps=100)
+                    rep(f"GMM_CARRY_F{F}@{M}x{N}", t, M * N, nbytes + 4 * (N * F + M * (F + 1)),
+                        {"splits": _lib.num_splits(_lib.WS_GMM_CARRY, M, N)})
     if only is None or "EXT_JAC" in only:
         # the velocity-gradient pass (csrc/ext_jac.hip) next to its yardstick, the external-point
         # forward with the divergence row, at the same N x M: back-to-back launches, alternated

@@ -24,7 +24,7 @@ KBASE, KREDSCAL, KRED, GRADK, GRADK_REV, DDK, GENDK, HESSK, LAPK, GRADLAPK, GRAD
 # enum dicp_ws_kind
 WS_RED, WS_ODE_SELF_FWD, WS_ODE_SELF_BWD, WS_ODE_EXT_FWD, WS_ODE_EXT_BWD, WS_GMM_ESTEP, \
     WS_GMM_MSTEP, WS_GMM_TARGETS, WS_RIDGE_CG, WS_ODE_SELF_FWD_ROWS, WS_ODE_SELF_BWD_PART, WS_GRAD, \
-    WS_ODE_SELF_FWD_PHASED, WS_GMM_ASSIGN, WS_ODE_EXT_JAC, WS_ODE_EXT_INV = range(16)
+    WS_ODE_SELF_FWD_PHASED, WS_GMM_ASSIGN, WS_ODE_EXT_JAC, WS_ODE_EXT_INV, WS_GMM_CARRY = range(17)
 # enum dicp_grad_kind
 GRAD_HESSW, GRAD_HESSWP, GRAD_ZDOTV, GRAD_HESS3, GRAD_GRADLAP3 = range(5)
 
@@ -57,6 +57,7 @@ _SIGNATURES = {
     "dicp_gmm_mstep_f32": [_P, _P, _I64, _P, _P, _I64, _INT, _DBL, _P, _P, _SZ, _P],
     "dicp_gmm_targets_f32": [_P, _P, _I64, _P, _P, _DBL, _P, _P, _I64, _INT, _P, _P, _SZ, _P],
     "dicp_gmm_assign_f32": [_P, _I64, _P, _P, _I64, _INT, _DBL, _INT, _P, _P, _P, _SZ, _P],
+    "dicp_gmm_carry_f32": [_P, _I64, _P, _P, _P, _I64, _INT, _INT, _DBL, _P, _P, _P, _SZ, _P],
     "dicp_lddmm_ode_self_fwd_rows_f32": [_P, _P, _I64, _I64, _I64, _INT, _DBL, _DBL, _P, _P, _P, _P,
                                          _P, _SZ, _P],
     "dicp_lddmm_euler_step_rows_f32": [_P, _P, _I64, _I64, _I64, _INT, _DBL, _DBL, _DBL, _P, _P, _P,
@@ -310,6 +311,9 @@ FLOPS_PER_PAIR = {
     "gmm_targets": 32, "ridge_cg": 15,
     # 3 sub + mul + 3 fma and the compare / select of the running best; no exp
     "gmm_assign": 13,
+    # soft transfer (csrc/carry.hip) with one channel: 3 sub + mul + 3 fma, the shift, one exp2,
+    # the sum and one fma (each further channel of a block adds one fma, not priced)
+    "gmm_carry": 16,
     # velocity gradient at carried points (csrc/ext_jac.hip), eta = 0: 3 sub + 3 fma + mul, one
     # exp2, 3 mul + 3 add + 9 fma
     "ode_ext_jac": 35,
@@ -992,6 +996,40 @@ def gmm_assign(rows, cols, bias, sigma: float, k: int = 1):
                                                    k, _ptr(idx), _ptr(val), _ptr(ws), nb, _stream(dev)))
     _check_rc(rc, "gmm_assign")
     return idx, val
+
+
+def gmm_carry(rows, cols, bias, feat, sigma: float):
+    """Fused responsibility-weighted mean (dicp_gmm_carry_f32): with the logits
+    e_ij = bias_j - log2(e) |rows_i - cols_j|^2 / (2 sigma^2) over the columns j,
+    lse2_i = log2 sum_j 2^e_ij and out_i = sum_j 2^(e_ij - lse2_i) feat_j.  bias: (N,) float32 in
+    the log2 domain (-inf: a dead column, which contributes nothing whatever its feat), or None
+    (zeros); feat (N, F), F >= 1.  Returns (out float32 (M, F), lse2 float32 (M,)); without a
+    live column lse2 = -inf and out = NaN, a row with a non-finite coordinate holds NaN."""
+    rows = _dev(rows, "rows")
+    cols = _dev(cols, "cols")
+    feat = _dev(feat, "feat")
+    M, D = rows.shape
+    N = cols.shape[0]
+    if cols.shape[1] != D:
+        raise ValueError(f"gmm_carry: rows are {D}-dimensional, cols {cols.shape[1]}-dimensional")
+    if feat.dim() != 2 or feat.shape[0] != N or feat.shape[1] < 1:
+        raise ValueError(f"gmm_carry: feat must be shaped ({N}, F), F >= 1")
+    F = feat.shape[1]
+    if bias is not None:
+        bias = _dev(bias, "bias")
+        if bias.shape != (N,):
+            raise ValueError(f"gmm_carry: bias must be shaped ({N},)")
+    dev = rows.device
+    out = torch.empty((M, F), device=dev, dtype=torch.float32)
+    lse2 = torch.empty(M, device=dev, dtype=torch.float32)
+    ws, nb = (None, 0) if M == 0 else _workspace(WS_GMM_CARRY, M, N, D, dev)
+    nblk = (F + 15) // 16       # channel blocks: each is a pass over all pairs
+    rc = _launch("gmm_carry", M * N * nblk, 4 * (nblk * (M + N) * (D + 1) + (M + N) * F + M),
+                 lambda: lib().dicp_gmm_carry_f32(_ptr(rows), M, _ptr(cols), _ptr(bias), _ptr(feat), N, F, D,
+                                                  float(sigma), _ptr(out), _ptr(lse2), _ptr(ws), nb,
+                                                  _stream(dev)))
+    _check_rc(rc, "gmm_carry")
+    return out, lse2
 
 
 # ---------------------------------------------------------------------------------------

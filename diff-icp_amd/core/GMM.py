@@ -42,6 +42,10 @@ _LN2 = 0.6931471805599453
 
 # GaussianMixtureUnif.assign's result: index (N, k) int64, log_resp (N, k), log_outlier (N,) or None
 Assignment = collections.namedtuple("Assignment", ["index", "log_resp", "log_outlier"])
+# carry_to_points' result: values (N,) or (N, F), log_outlier (N,) or None
+Carried = collections.namedtuple("Carried", ["values", "log_outlier"])
+# pool_from_points' result: values (C,) or (C, F), mass (C,)
+Pooled = collections.namedtuple("Pooled", ["values", "mass"])
 
 
 def _comm_active(comm):
@@ -262,6 +266,77 @@ class GaussianMixtureUnif(torch.nn.Module):
         log_resp = _LN2 * (val + w2[:, None])
         dead = torch.isinf(w2)[:, None].expand_as(idx)
         return torch.where(dead, torch.full_like(idx, -1), idx).long(), log_resp
+
+    # ------------------------------------------------------------------------------------
+    # Soft transfer of fields through the match (no reference counterpart at size: the dense
+    # log_responsibilities is the only route there), csrc/carry.hip
+    def _field(self, values, n, what):
+        """values (n,) or (n, F) -> ((n, F) float32 on the model's spec, whether it was 1-D)."""
+        v = torch.as_tensor(values).detach().to(**self.spec)
+        flat = v.dim() == 1
+        if flat:
+            v = v[:, None]
+        if v.dim() != 2 or v.shape[0] != n or v.shape[1] < 1:
+            raise ValueError(f"{what}: values must be shaped ({n},) or ({n}, F), F >= 1; "
+                             f"got {tuple(torch.as_tensor(values).shape)}")
+        return v.contiguous(), flat
+
+    def carry_to_points(self, X, values):
+        """Component attributes carried to the points of X (N, D) as the posterior mean
+        sum_c r_nc values_c, r normalised over the components (the convention of
+        log_responsibilities and assign), at any size: one fused pass, nothing N x C is formed.
+        values: (C,) or (C, F) on the components (label probabilities, a template scalar map).
+        Returns Carried(values, log_outlier): values (N,) or (N, F); log_outlier (N,) as in
+        assign (None for a mixture without outliers; ValueError if vol0 is unset).  A dead
+        component (w = -inf) contributes nothing, whatever its values.  Inputs are detached; the
+        model is not changed; not differentiable."""
+        if self.outliers is not None and self.outliers["vol0"] is None:
+            raise ValueError("carry_to_points: the outlier reference volume vol0 is not set (set_vol0)")
+        V, flat = self._field(values, self.C, "carry_to_points")
+        X = X.detach().to(**self.spec).contiguous()
+        mu = self.mu.detach().contiguous()
+        _, w2, _ = self._columns(mu, self.w.detach())
+        out, lse2 = _lib.gmm_carry(X, mu, w2, V, float(self.sigma))
+        log_outlier = None
+        if self.outliers is not None:
+            lgn = self.D * (np.log(float(self.sigma)) + 0.5 * np.log(2 * math.pi))
+            T = _LN2 * lse2 - lgn             # the E-step's T_n, from the same pass
+            eta0_n = self.outliers["eta0"] - np.log(self.outliers["vol0"]) - T
+            log_outlier, _ = self.log_ratio_to_proba(eta0_n)
+        return Carried(out[:, 0] if flat else out, log_outlier)
+
+    def pool_from_points(self, X, values, weights=None):
+        """A per-point field pooled onto the components: sum_n gamma_nc g_n / sum_n gamma_nc with
+        gamma_nc = r_nc (1 - gamma0_n) [weights_n] -- r normalised over the components, the
+        outlier posterior gamma0_n discounting a point (the E-step's gamma_T; 0 without
+        outliers) -- at any size: one stats-less E-step and one fused pass.
+        values: (N,) or (N, F) on the points; weights: optional (N,) >= 0.
+        Returns Pooled(values, mass): values (C,) or (C, F), mass (C,) = sum_n gamma_nc.  A dead
+        component or a component of zero mass holds NaN values and mass 0.  Inputs are detached;
+        the model is not changed; not differentiable.  Under a communicator (a sharded atlas) X
+        is this rank's points: the answer is over the local rows only, nothing is exchanged."""
+        if self.outliers is not None and self.outliers["vol0"] is None:
+            raise ValueError("pool_from_points: the outlier reference volume vol0 is not set (set_vol0)")
+        V, flat = self._field(values, X.shape[0], "pool_from_points")
+        X, mu, w2, T, T2 = self._row_lse(X)
+        bias = -T2
+        if self.outliers is not None:
+            eta0_n = self.outliers["eta0"] - np.log(self.outliers["vol0"]) - T
+            _, lgammaT_n = self.log_ratio_to_proba(eta0_n)
+            bias = bias + _LOG2E * lgammaT_n
+        if weights is not None:
+            wn = torch.as_tensor(weights).detach().to(**self.spec)
+            if wn.shape != (X.shape[0],):
+                raise ValueError(f"pool_from_points: weights must be shaped ({X.shape[0]},)")
+            bias = bias + torch.log2(wn)      # weight 0: a dead column
+        # a point without a finite LSE (NaN coordinates, or no live component) pools nowhere
+        bias = torch.where(torch.isfinite(T2), bias, torch.full_like(bias, float("-inf")))
+        out, lse2 = _lib.gmm_carry(mu, X, bias.contiguous(), V, float(self.sigma))
+        mass = torch.exp2(lse2 + w2)
+        empty = ~(mass > 0)                   # dead component, no live point, or underflow
+        mass = torch.where(empty, torch.zeros_like(mass), mass)
+        out = torch.where(empty[:, None], torch.full_like(out, float("nan")), out)
+        return Pooled(out[:, 0] if flat else out, mass)
 
     # ------------------------------------------------------------------------------------
     def EM_step_hip(self, X, skip_M=False):

@@ -20,7 +20,8 @@ import copy
 import numpy as np
 import torch
 
-from .GMM import Assignment, GaussianMixtureUnif, _comm_active, _gather_rows, _sum_ranks
+from .GMM import (Assignment, Carried, GaussianMixtureUnif, Pooled, _comm_active, _exchange, _gather_rows,
+                  _sum_ranks)
 from .LDDMM import LDDMMModel
 from .registrations import LDDMMRegistration
 from ..tools.in_out import read_point_sets
@@ -148,6 +149,58 @@ class MultiPSR:
             return Assignment(a.index.to(dev), a.log_resp.to(**self.dataspec), lo)
         index, log_resp = self.GMMi[s].nearest_points(X, k=topk)
         return index.to(dev), log_resp.to(**self.dataspec)
+
+    def carry_to_frame(self, values, k=0, s=0):
+        """Template values -- (C,) or (C, F) on the components of GMMi[s]: label probabilities, a
+        template scalar map -- carried to the warped points x1[k, s] of frame k as their posterior
+        mean (GaussianMixtureUnif.carry_to_points; no reference counterpart).  Returns
+        Carried(values (N_ks,) or (N_ks, F), log_outlier).  Computed on the compute spec, returned
+        on the data spec; changes no state."""
+        X = self.x1[k, s].to(**self.compspec)
+        c = self.GMMi[s].carry_to_points(X, torch.as_tensor(values).to(**self.compspec))
+        lo = None if c.log_outlier is None else c.log_outlier.to(**self.dataspec)
+        return Carried(c.values.to(**self.dataspec), lo)
+
+    def pool_to_template(self, values, s=0, weights=None):
+        """Per-point fields of the frames pooled onto the components of GMMi[s] through the soft
+        match of the warped points x1[k, s] (GaussianMixtureUnif.pool_from_points per frame; no
+        reference counterpart): with the frames' pooled values v_k and masses mass_k,
+        values = sum_k mass_k v_k / sum_k mass_k and mass = sum_k mass_k, combined in float64;
+        a frame without mass on a component is left out of that component's sum.
+        values: a list of length K or a dict by frame, values[k] (N_ks,) or (N_ks, F) for each of
+        this rank's frames (other entries are not read); weights: optional, the same layout,
+        (N_ks,) >= 0 or None per frame.  Returns Pooled(values (C,) or (C, F), mass (C,)); NaN
+        values where no frame has mass.  Sharded: one exchange over the ranks, every rank (each
+        must own a frame) holds the same result.  Computed on the compute spec, returned on the
+        data spec; changes no state."""
+        g = self.GMMi[s]
+        # nothing is exchanged per frame (pool_from_points covers the local rows anyway)
+        num, den, flat = None, None, None
+        for k in self.frames:
+            X = self.x1[k, s].to(**self.compspec)
+            w = None if weights is None else weights[k]
+            if w is not None:
+                w = torch.as_tensor(w).to(**self.compspec)
+            p = g.pool_from_points(X, torch.as_tensor(values[k]).to(**self.compspec), weights=w)
+            v, m = p.values.double(), p.mass.double()
+            f = v.dim() == 1
+            if f:
+                v = v[:, None]
+            if num is not None and (f != flat or v.shape != num.shape):
+                raise ValueError("pool_to_template: the frames' values differ in their channels")
+            live = m > 0
+            t = torch.where(live[:, None], m[:, None] * v, torch.zeros_like(v))
+            num = t if num is None else num + t
+            den = m if den is None else den + m
+            flat = f
+        if num is None:
+            raise ValueError("pool_to_template: this rank owns no frame")
+        if self.world > 1:
+            ex = _exchange({"num": num, "den": den}, self.comm)
+            num, den = ex["num"].sum(0), ex["den"].sum(0)
+        out = num / den[:, None]                 # 0 / 0 = NaN: no mass anywhere
+        out = out[:, 0] if flat else out
+        return Pooled(out.to(**self.dataspec), den.to(**self.dataspec))
 
     def transfer(self, X, k_from, k_to):
         """The points X of frame k_from's data space carried into frame k_to's:

@@ -404,6 +404,29 @@ int dicp_gmm_assign_f32(const float* rows, int64_t M, const float* cols, const f
                         int D, double sigma, int K, int32_t* idx, float* val,
                         void* ws, size_t ws_bytes, dicp_stream_t stream);
 
+/* Soft label / field transfer (extends the dense (N, C) log_responsibilities, GMM.py:221-232,
+ * and the M-step's responsibility-weighted means, GMM.py:286-299, to any feature matrix): a
+ * fused softmax over the columns of Gaussian logits applied to feat,
+ *   e_ij     = bias_j - k2 |rows_i - cols_j|^2,   k2 = log2(e) / (2 sigma^2)   (log2 domain)
+ *   lse2_i   = log2 sum_j 2^e_ij
+ *   out_i,f  = sum_j 2^(e_ij - lse2_i) feat_j,f
+ * rows (M, D), cols (N, D), bias (N,) or NULL (reads as 0), feat (N, F) row-major; D = 2 or 3,
+ * F >= 1; out (M, F), lse2 (M,) or NULL.  The squared distance is formed from the coordinate
+ * differences and the running reference of every row is kept by the kernel: any finite input is
+ * handled, no shift comes from the caller.  Deterministic (no atomics; chunk partials merged in
+ * chunk order); a channel's bits do not depend on F (channels go in blocks of at most 16).
+ * A column with bias = -inf is dead: it contributes nothing whatever its feat (NaN included).
+ * N = 0 or no live column: lse2 = -inf, out = NaN.  A row with a non-finite coordinate: lse2 =
+ * NaN, out = NaN.  A non-finite feat in a live column makes that channel non-finite in every row.
+ * Points -> components: rows = X, cols = mu, bias = w2, feat = component attributes.
+ * Components -> points: rows = mu, cols = X, bias = -T2 + log2 (1 - gamma0), feat = a point field.
+ * M = 0 launches nothing.  Any other D, F < 1: DICP_ERR_INVALID.
+ * Workspace kind DICP_WS_GMM_CARRY (M = rows, N = columns; no F argument: one channel block).
+ * Not batchable. */
+int dicp_gmm_carry_f32(const float* rows, int64_t M, const float* cols, const float* bias,
+                       const float* feat, int64_t N, int F, int D, double sigma, float* out,
+                       float* lse2, void* ws, size_t ws_bytes, dicp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Momenta from speeds (LDDMMModel.v2p, LDDMM.py:235-253): ridge solve
  *   (K(x,x) + alpha I) b = v,   x (M,D), v, b (M,D)
@@ -457,8 +480,9 @@ enum dicp_ws_kind {
   DICP_WS_GMM_ASSIGN = 13,       /* dicp_gmm_assign_f32: M = rows, N = columns */
   DICP_WS_ODE_EXT_JAC = 14,      /* dicp_lddmm_ode_ext_jac_f32 / dicp_lddmm_ext_jac_step_f32: M = support
                                     points, N = carried points (as DICP_WS_ODE_EXT_FWD) */
-  DICP_WS_ODE_EXT_INV = 15       /* dicp_lddmm_ext_inv_step_f32: M = support points, N = carried points;
+  DICP_WS_ODE_EXT_INV = 15,      /* dicp_lddmm_ext_inv_step_f32: M = support points, N = carried points;
                                     the slabs of DICP_WS_ODE_EXT_JAC and N (D + D^2) floats of scratch */
+  DICP_WS_GMM_CARRY = 16         /* dicp_gmm_carry_f32: M = rows, N = columns */
 };
 size_t dicp_workspace_bytes(int kind, int64_t M, int64_t N, int D);
 
