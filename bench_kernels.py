@@ -34,6 +34,9 @@ FLOPS_PER_PAIR = {
     # soft transfer (csrc/carry.hip): 3 sub + mul + 3 fma, the shift, the sum of the exps (+ 1 exp)
     # and one fma per channel
     "GMM_CARRY_F1": 14 + 2 * 1, "GMM_CARRY_F4": 14 + 2 * 4, "GMM_CARRY_F16": 14 + 2 * 16,
+    # RKHS Gram entries (csrc/gram.hip): 3 sub + mul + 2 fma, mul + 2 fma, the exponent's mul,
+    # the fma into the tile sum (+ 1 exp); the composed route is one KRed per pair (15)
+    "RKHS_GRAM": 17, "GRAM_BY_KRED": 15,
     "ODE_EXT_FWD": 22,        # v and the divergence row (eta = 0): 3 sub + mul + 7 fma
     "EXT_JAC": 35, "EXT_JAC_STEP": 35,   # v and the D x D gradient (eta = 0): 3 sub + 4 mul + 3 add + 12 fma
 }
@@ -181,6 +184,34 @@ def main():
                     t = timed(lambda: _lib.gmm_carry(rows, cols, bias, feats[F], 0.05), reps=100)
                     rep(f"GMM_CARRY_F{F}@{M}x{N}", t, M * N, nbytes + 4 * (N * F + M * (F + 1)),
                         {"splits": _lib.num_splits(_lib.WS_GMM_CARRY, M, N)})
+    if only is None or "GRAM" in only:
+        # all K (K + 1) / 2 inner products of an atlas' fields: one rkhs_gram call next to the
+        # route the reductions allow, (p_a * KRed(q_a, q_b, p_b)).sum() per pair (float64 sum of
+        # the float32 rows, no host read), in the same process, alternated three times
+        K, M = (8, 20000) if args.quick else (32, 20000)
+        qs = [torch.rand(M, D, device=dev) for _ in range(K)]
+        ps = [0.01 * torch.randn(M, D, device=dev) for _ in range(K)]
+        q, p = torch.cat(qs), torch.cat(ps)
+        offsets = [k * M for k in range(K + 1)]
+        pairs = torch.triu_indices(K, K).t().contiguous()
+        npairs = pairs.shape[0]
+
+        def composed():
+            out = torch.empty(npairs, device=dev, dtype=torch.float64)
+            for n, (a, b) in enumerate(pairs.tolist()):
+                out[n] = (ps[a].double() * _lib.gauss_red(_lib.KRED, qs[a], qs[b], 0.1, b=ps[b]).double()).sum()
+            return out
+
+        nbytes = 4 * 2 * D * 2 * M * npairs
+        for _ in range(3):
+            t = timed(lambda: _lib.rkhs_gram(q, p, offsets, pairs, 0.1), warm=1, reps=3)
+            rep(f"RKHS_GRAM@{K}x{M}", t, npairs * M * M, nbytes + 8 * npairs,
+                {"pairs": npairs, "splits": _lib.num_splits(_lib.WS_RKHS_GRAM, M, npairs)})
+            t = timed(composed, warm=1, reps=1)
+            rep(f"GRAM_BY_KRED@{K}x{M}", t, npairs * M * M, nbytes + 4 * D * M * npairs, {"pairs": npairs})
+        g1, g2 = _lib.rkhs_gram(q, p, offsets, pairs, 0.1), composed()
+        print(json.dumps({"gram_vs_composed_max_rel": float(((g1 - g2).abs() / g1.abs().max()).max())}),
+              flush=True)
     if only is None or "EXT_JAC" in only:
         # the velocity-gradient pass (csrc/ext_jac.hip) next to its yardstick, the external-point
         # forward with the divergence row, at the same N x M: back-to-back launches, alternated

@@ -24,7 +24,8 @@ KBASE, KREDSCAL, KRED, GRADK, GRADK_REV, DDK, GENDK, HESSK, LAPK, GRADLAPK, GRAD
 # enum dicp_ws_kind
 WS_RED, WS_ODE_SELF_FWD, WS_ODE_SELF_BWD, WS_ODE_EXT_FWD, WS_ODE_EXT_BWD, WS_GMM_ESTEP, \
     WS_GMM_MSTEP, WS_GMM_TARGETS, WS_RIDGE_CG, WS_ODE_SELF_FWD_ROWS, WS_ODE_SELF_BWD_PART, WS_GRAD, \
-    WS_ODE_SELF_FWD_PHASED, WS_GMM_ASSIGN, WS_ODE_EXT_JAC, WS_ODE_EXT_INV, WS_GMM_CARRY = range(17)
+    WS_ODE_SELF_FWD_PHASED, WS_GMM_ASSIGN, WS_ODE_EXT_JAC, WS_ODE_EXT_INV, WS_GMM_CARRY, \
+    WS_RKHS_GRAM = range(18)
 # enum dicp_grad_kind
 GRAD_HESSW, GRAD_HESSWP, GRAD_ZDOTV, GRAD_HESS3, GRAD_GRADLAP3 = range(5)
 
@@ -58,6 +59,7 @@ _SIGNATURES = {
     "dicp_gmm_targets_f32": [_P, _P, _I64, _P, _P, _DBL, _P, _P, _I64, _INT, _P, _P, _SZ, _P],
     "dicp_gmm_assign_f32": [_P, _I64, _P, _P, _I64, _INT, _DBL, _INT, _P, _P, _P, _SZ, _P],
     "dicp_gmm_carry_f32": [_P, _I64, _P, _P, _P, _I64, _INT, _INT, _DBL, _P, _P, _P, _SZ, _P],
+    "dicp_rkhs_gram_f32": [_P, _P, _P, _INT, _I64, _P, _INT, _INT, _DBL, _P, _P, _SZ, _P],
     "dicp_lddmm_ode_self_fwd_rows_f32": [_P, _P, _I64, _I64, _I64, _INT, _DBL, _DBL, _P, _P, _P, _P,
                                          _P, _SZ, _P],
     "dicp_lddmm_euler_step_rows_f32": [_P, _P, _I64, _I64, _I64, _INT, _DBL, _DBL, _DBL, _P, _P, _P,
@@ -314,6 +316,9 @@ FLOPS_PER_PAIR = {
     # soft transfer (csrc/carry.hip) with one channel: 3 sub + mul + 3 fma, the shift, one exp2,
     # the sum and one fma (each further channel of a block adds one fma, not priced)
     "gmm_carry": 16,
+    # RKHS Gram entries (csrc/gram.hip), from the kernel's pair body: 3 sub + mul + 2 fma for
+    # |z|^2, mul + 2 fma for p_i . p_j, the exponent's mul, one exp2 and the fma into the tile sum
+    "rkhs_gram": 17,
     # velocity gradient at carried points (csrc/ext_jac.hip), eta = 0: 3 sub + 3 fma + mul, one
     # exp2, 3 mul + 3 add + 9 fma
     "ode_ext_jac": 35,
@@ -1030,6 +1035,49 @@ def gmm_carry(rows, cols, bias, feat, sigma: float):
                                                   _stream(dev)))
     _check_rc(rc, "gmm_carry")
     return out, lse2
+
+
+def rkhs_gram(q, p, offsets, pairs, sigma: float):
+    """RKHS Gram entries of a ragged list of momentum fields (dicp_rkhs_gram_f32): q, p (T, D)
+    float32 on the device hold the points and momenta of F fields one after the other, field f =
+    rows [offsets[f], offsets[f + 1]); for every pair n = (a, b) of `pairs`
+        out[n] = sum_{i in a} sum_{j in b} (p_i . p_j) exp(-|q_i - q_j|^2 / (2 sigma^2)),
+    summed in float64 above float32 tiles.  offsets: F + 1 integers, pairs: (npairs, 2) integers
+    (sequences or tensors; a device tensor is read back once: both are validated here, the
+    library does not).  Returns a float64 device tensor (npairs,): bitwise reproducible, and each
+    entry independent of the other pairs of the call given the largest field size.  One pair-sum
+    launch and one merge launch, whatever the sizes."""
+    q = _dev(q, "q")
+    p = _dev(p, "p")
+    if q.dim() != 2 or p.shape != q.shape:
+        raise ValueError(f"rkhs_gram: q and p must both be shaped (T, D), got {tuple(q.shape)} and "
+                         f"{tuple(p.shape)}")
+    T, D = q.shape
+    off = torch.as_tensor(offsets).detach().cpu().to(torch.int64).reshape(-1)
+    F = off.numel() - 1
+    if F < 0 or int(off[0]) < 0 or int(off[-1]) > T or bool((off[1:] < off[:-1]).any()):
+        raise ValueError(f"rkhs_gram: offsets must be F + 1 non-decreasing row indices within [0, {T}]")
+    pr = torch.as_tensor(pairs).detach().cpu().to(torch.int32).reshape(-1, 2)
+    npairs = pr.shape[0]
+    if npairs and (int(pr.min()) < 0 or int(pr.max()) >= F):
+        raise ValueError(f"rkhs_gram: pair indices must lie in [0, {F})")
+    dev = q.device
+    out = torch.empty(npairs, device=dev, dtype=torch.float64)
+    if npairs == 0:
+        return out
+    sizes = off[1:] - off[:-1]
+    max_rows = int(sizes.max())
+    work = int((sizes[pr[:, 0].long()] * sizes[pr[:, 1].long()]).sum())
+    rows = int((sizes[pr[:, 0].long()] + sizes[pr[:, 1].long()]).sum())
+    off_d = off.to(dev)
+    pr_d = pr.contiguous().to(dev)
+    ws, nb = _workspace(WS_RKHS_GRAM, max_rows, npairs, D, dev)
+    rc = _launch("rkhs_gram", work, 4 * 2 * D * rows + 8 * npairs,
+                 lambda: lib().dicp_rkhs_gram_f32(_ptr(q), _ptr(p), _ptr(off_d), F, max_rows, _ptr(pr_d),
+                                                  npairs, D, float(sigma), _ptr(out), _ptr(ws), nb,
+                                                  _stream(dev)))
+    _check_rc(rc, "rkhs_gram")
+    return out
 
 
 # ---------------------------------------------------------------------------------------

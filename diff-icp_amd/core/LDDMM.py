@@ -383,6 +383,65 @@ class LDDMMModel:
         getspec(x, q, p)
         return _lib.ode_ext_jac(x.detach(), q.detach(), p.detach(), self.Kernel.sigma, float(self.eta))[1]
 
+    # ------------------------------------------------------------------------------------
+    # RKHS inner products of velocity fields (extension; csrc/gram.hip)
+    def _gram_fields(self, fields, what):
+        out = []
+        for k, f in enumerate(fields):
+            if not (isinstance(f, (tuple, list)) and len(f) == 2):
+                raise ValueError(f"field_gram: {what}[{k}] must be a pair (q, p) of tensors")
+            q, p = f
+            if not (isinstance(q, torch.Tensor) and isinstance(p, torch.Tensor)):
+                raise ValueError(f"field_gram: {what}[{k}] must be a pair (q, p) of tensors")
+            if q.dim() != 2 or q.shape[1] != self.D or p.shape != q.shape:
+                raise ValueError(f"field_gram: {what}[{k}] must hold q and p both shaped (n, {self.D}), got "
+                                 f"{tuple(q.shape)} and {tuple(p.shape)}")
+            out.append((q.detach(), p.detach()))
+        return out
+
+    def field_gram(self, fields, others=None):
+        """RKHS inner products <v_a, v_b>_V = sum_ij (p_i . p'_j) exp(-|q_i - q'_j|^2 / 2 sigma^2) of
+        the velocity fields of the momenta `fields` = [(q, p), ...], each on its own support, as a
+        float64 tensor: (F, F) when others is None -- the upper triangle is computed once and
+        mirrored, so the result is exactly symmetric -- or the (F, G) products of fields x others.
+        One _lib.rkhs_gram call (one pair-sum launch, float64 totals).  For a == b the entry is
+        2 Hamiltonian(q, p).  Inputs are detached.
+        Only for eta = 0 (classic / hybrid): with the gradient component the field of (q, p) is
+        affine in p, not linear (v = K p - eta grad K), so a weighted mean of fields over
+        different supports is not the field of any momenta and these sums are not its inner
+        products.  ValueError then, and on a field of the wrong shape, dtype or device."""
+        if self.eta != 0:
+            raise ValueError("field_gram needs eta = 0 (gradcomponent=False): with the gradient component "
+                             "the field is affine in the momenta, not linear, so a mean field over "
+                             "different supports is not a model field")
+        A = self._gram_fields(fields, "fields")
+        B = [] if others is None else self._gram_fields(others, "others")
+        both = A + B
+        if not both:
+            return torch.zeros((0, 0), dtype=torch.float64, device=self.Kernel.spec["device"])
+        try:
+            getspec(*[t for f in both for t in f])
+        except ValueError:
+            raise ValueError("field_gram: all fields must be on the same device and use the same dtype") from None
+        nF, nG = len(A), len(B)
+        offsets = [0]
+        for q, _ in both:
+            offsets.append(offsets[-1] + q.shape[0])
+        q = torch.cat([f[0] for f in both], dim=0).contiguous()
+        p = torch.cat([f[1] for f in both], dim=0).contiguous()
+        if others is None:
+            iu = torch.triu_indices(nF, nF)
+            g = _lib.rkhs_gram(q, p, offsets, iu.t(), self.Kernel.sigma)
+            G = torch.zeros((nF, nF), dtype=torch.float64, device=g.device)
+            iu = iu.to(g.device)
+            G[iu[0], iu[1]] = g
+            G[iu[1], iu[0]] = g
+            return G
+        pairs = [(a, nF + b) for a in range(nF) for b in range(nG)]
+        g = _lib.rkhs_gram(q, p, offsets, torch.tensor(pairs, dtype=torch.int32).reshape(-1, 2),
+                           self.Kernel.sigma)
+        return g.reshape(nF, nG)
+
     def _support_states(self, q0, p0, need_p1=False):
         """(Q, P) of Shoot(q0, p0), without reading or writing the model's shoot_cache (need_p1
         False: the final momenta may be left unformed, as in Shoot)."""

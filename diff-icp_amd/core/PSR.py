@@ -24,6 +24,7 @@ from .GMM import (Assignment, Carried, GaussianMixtureUnif, Pooled, _comm_active
                   _sum_ranks)
 from .LDDMM import LDDMMModel
 from .registrations import LDDMMRegistration
+from .statistics import TangentPCA
 from ..tools.in_out import read_point_sets
 from ..tools.spec import defspec
 from .support import decimated_points, grid_points, merged_v2p_args, warn_uncovered
@@ -337,6 +338,19 @@ class DiffPSR(MultiPSR):
         with torch.no_grad():
             mu = self.GMMi[s].mu.detach().to(**self.compspec)
             return self.Registration(k).inverse(mu).to(**self.dataspec)
+
+    def tangent_pca(self, side="target", rtol=TangentPCA.DEFAULT_RTOL):
+        """Tangent-space PCA of the K frames' registrations (core/statistics.py TangentPCA; no
+        reference counterpart): the fields are Registration(k).tangent_field(side).  side
+        "target" (default) is the template side for diff-ICP, whose registrations map each
+        frame's data onto the template; "source" compares the fields in the frames' own data
+        spaces.  Needs the eta = 0 models (classic / hybrid).  Single process only: under an
+        active communicator (sharded atlas) the frames' fields live on different ranks."""
+        if self.world > 1 or _comm_active(self.comm):
+            raise ValueError("tangent_pca: single process only (the frames of a sharded atlas live on "
+                             "different ranks)")
+        fields = [self.Registration(k).tangent_field(side) for k in range(self.K)]
+        return TangentPCA.fit(self.LMi, fields, rtol=rtol)
 
     def initialize_a0(self, **v2p_args):
         """a0 giving zero initial speeds (PSR.py:406-413)."""

@@ -28,8 +28,10 @@ from ..tools.in_out import read_point_sets
 from ..tools.kernel import GenKernel
 from ..tools.optim import LBFGS_optimization
 from ..tools.spec import defspec
+from .GMM import _comm_active
 from .LDDMM import LDDMMModel
 from .registrations import LDDMMRegistration
+from .statistics import TangentPCA
 from .support import decimated_points, grid_points, merged_v2p_args, split_rows, warn_uncovered
 
 
@@ -202,6 +204,19 @@ class DiffPSR_std(MultiPSR_std):
         self.q0 = self.ally0
         self.a0 = [None] * self.K
         self.initialize_a0()
+
+    def tangent_pca(self, side="source", rtol=TangentPCA.DEFAULT_RTOL):
+        """Tangent-space PCA of the K frames' registrations (core/statistics.py TangentPCA; no
+        reference counterpart): the fields are Registration(k).tangent_field(side).  side
+        "source" (default) is the template side for the standard model, whose registrations map
+        the templates onto each frame.  Needs the eta = 0 models (classic / hybrid).  Single
+        process only."""
+        comm = getattr(self, "comm", None)
+        if getattr(self, "world", 1) > 1 or _comm_active(comm):
+            raise ValueError("tangent_pca: single process only (the frames of a sharded atlas live on "
+                             "different ranks)")
+        fields = [self.Registration(k).tangent_field(side) for k in range(self.K)]
+        return TangentPCA.fit(self.LMi, fields, rtol=rtol)
 
     def initialize_a0(self, **v2p_args):
         """Momenta of zero initial speed (PSR_standard.py:422-428)."""

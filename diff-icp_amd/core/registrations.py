@@ -67,6 +67,20 @@ class LDDMMRegistration(Registration):
         return self.shoot(Y, backward=True, previous_forwardshoot=previous_forwardshoot)[-1][3]
 
     # ------------------------------------------------------------------------------------
+    # The registration as a tangent vector (extension; core/statistics.py)
+    def tangent_field(self, side="source"):
+        """The momenta (q, p) whose velocity field is this registration's tangent vector, detached:
+        side "source": (q0, a0), the initial field, in the space apply() starts from; "target":
+        (q1, -p1) of the forward shoot (formed with its final momenta), the state the reference's
+        `backward` shoots from, in the space apply() arrives in.  Nothing of the model changes."""
+        if side == "source":
+            return self.q0.detach(), self.a0.detach()
+        if side != "target":
+            raise ValueError(f"unknown side : {side}. Choices are 'source' or 'target'")
+        Q, P = self.LMi._support_states(self.q0.detach(), self.a0.detach(), need_p1=True)
+        return Q[-1], -P[-1]
+
+    # ------------------------------------------------------------------------------------
     # Exact inverse of the map apply() computes (extension; LDDMMModel.flow_inverse)
     def inverse(self, Y, previous_forwardshoot=None, tol=None, max_iter=10, return_info=False):
         """X with apply(X) = Y: the inverse of the discrete flow itself, by Newton's iteration on

@@ -427,6 +427,38 @@ int dicp_gmm_carry_f32(const float* rows, int64_t M, const float* cols, const fl
                        const float* feat, int64_t N, int F, int D, double sigma, float* out,
                        float* lse2, void* ws, size_t ws_bytes, dicp_stream_t stream);
 
+/* RKHS Gram entries of a ragged list of momentum fields (no reference counterpart; the inner
+ * products tangent-space statistics of an atlas need, core/statistics.py): for every listed pair
+ * n = (a, b) of fields,
+ *   out[n] = sum_{i in a} sum_{j in b} (p_i . p_j) exp(-|q_i - q_j|^2 / (2 sigma^2))
+ * over all ordered (i, j) -- <v_a, v_b>_V of the eta = 0 fields; for a == b the diagonal is
+ * included, i.e. twice the eta = 0 Hamiltonian.
+ * q, p (T, D) float32: the points and momenta of F fields one after the other; offsets (F + 1,)
+ * int64 on the device, field f = rows [offsets[f], offsets[f + 1]); max_rows: the largest field
+ * size, given by the caller (the launcher reads no device memory; a smaller value than the truth
+ * leaves rows and columns out); pairs (npairs, 2) int32 on the device, repeats and a == b
+ * allowed; out (npairs,) float64 on the device.  D = 2 or 3.
+ * Pair indices and offsets are NOT validated (they live on the device): an index outside
+ * [0, F) or offsets that leave (T, D) are the caller's error (the Python layer checks them).
+ * Arithmetic: the squared distance from the coordinate differences; a pair term in float32, in
+ * the log2 domain with one v_exp_f32; a lane sums one staged tile of at most 256 terms per row
+ * in float32 (one fused multiply-add per term); every sum above a tile -- lane totals, the
+ * workgroup's reduction, the partials of row blocks and column chunks -- is float64.
+ * Deterministic: no atomics; exactly one pair-sum launch (every workgroup writes one partial
+ * into its own workspace slot) and one merge launch (fixed order) per call, whatever npairs and
+ * the sizes (max_rows = 0: the merge launch alone).  out[n] is bitwise reproducible and
+ * depends on the pair's two fields, sigma and max_rows only, not on the other pairs or fields of
+ * the call.
+ * An empty field gives 0.0 for its pairs.  A non-finite coordinate or momentum makes exactly
+ * the pairs that contain its field (and whose other field is not empty) non-finite.
+ * npairs = 0 launches nothing.  D outside {2, 3}, F < 0, npairs < 0, max_rows < 0 (or beyond
+ * 65535 * 512), sigma <= 0, a null pointer where data is needed: DICP_ERR_INVALID, before any
+ * device work.  Workspace kind DICP_WS_RKHS_GRAM (M = max_rows, N = npairs); dicp_num_splits
+ * answers the column chunks of a pair of max_rows-point fields.  Not batchable. */
+int dicp_rkhs_gram_f32(const float* q, const float* p, const int64_t* offsets, int F, int64_t max_rows,
+                       const int32_t* pairs, int npairs, int D, double sigma,
+                       double* out, void* ws, size_t ws_bytes, dicp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Momenta from speeds (LDDMMModel.v2p, LDDMM.py:235-253): ridge solve
  *   (K(x,x) + alpha I) b = v,   x (M,D), v, b (M,D)
@@ -482,7 +514,8 @@ enum dicp_ws_kind {
                                     points, N = carried points (as DICP_WS_ODE_EXT_FWD) */
   DICP_WS_ODE_EXT_INV = 15,      /* dicp_lddmm_ext_inv_step_f32: M = support points, N = carried points;
                                     the slabs of DICP_WS_ODE_EXT_JAC and N (D + D^2) floats of scratch */
-  DICP_WS_GMM_CARRY = 16         /* dicp_gmm_carry_f32: M = rows, N = columns */
+  DICP_WS_GMM_CARRY = 16,        /* dicp_gmm_carry_f32: M = rows, N = columns */
+  DICP_WS_RKHS_GRAM = 17         /* dicp_rkhs_gram_f32: M = max_rows, N = npairs */
 };
 size_t dicp_workspace_bytes(int kind, int64_t M, int64_t N, int D);
 
