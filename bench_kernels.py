@@ -39,6 +39,9 @@ FLOPS_PER_PAIR = {
     "RKHS_GRAM": 17, "GRAM_BY_KRED": 15,
     "ODE_EXT_FWD": 22,        # v and the divergence row (eta = 0): 3 sub + mul + 7 fma
     "EXT_JAC": 35, "EXT_JAC_STEP": 35,   # v and the D x D gradient (eta = 0): 3 sub + 4 mul + 3 add + 12 fma
+    # tangent-linear pass (csrc/tlm.hip): 66 per self pair and 32 per carried pair, M = N: 49 on
+    # average; the central difference pays 2 x (33 + 22) per such pair of pairs
+    "TLM": 49, "TLM_BY_DIFFERENCE": 55,
 }
 # HBM bytes per launch (algorithmic: each input read once, each output written once).
 
@@ -259,6 +262,43 @@ def main():
             rep(f"API_APPLY_WITH_JACOBIAN@{N}x{M}", t, 10 * N * M, 0)
             t = timed(lambda: LM.flow_jacobian(reg.q0, reg.a0, X, shoot=sh), warm=1, reps=5)
             rep(f"API_FLOW_JACOBIAN_GIVEN_SHOOT@{N}x{M}", t, 10 * N * M, 0)
+    if only is None or "TLM" in only:
+        # one tangent-linear pass (self + carried part, csrc/tlm.hip) for L directions next to what
+        # a central difference pays per direction on the forward kernels -- two self forwards and
+        # two external-point forwards at the displaced states -- in the same process, alternated
+        # three times; then the pass with 1 and 2 row pairs per thread forced (option pk_rp)
+        for M in ([20000] if args.quick else [20000, 100000]):
+            N = M
+            q, x = torch.rand(M, D, device=dev), torch.rand(N, D, device=dev)
+            p = 0.01 * torch.randn(M, D, device=dev)
+            for L in (1, 4):
+                dq, dp = 0.1 * torch.randn(L, M, D, device=dev), 0.01 * torch.randn(L, M, D, device=dev)
+                dx = 0.1 * torch.randn(L, N, D, device=dev)
+                h = 1e-3
+                states = [(q + s * h * dq[l], p + s * h * dp[l], x + s * h * dx[l])
+                          for l in range(L) for s in (1.0, -1.0)]
+
+                def difference():
+                    for qs, ps, xs in states:
+                        _lib.ode_self_fwd(qs, ps, 0.1, 0.0, False)
+                        _lib.ode_ext_fwd(xs, qs, ps, 0.1, 0.0, False)
+
+                pairs = L * M * (M + N)
+                nb = 4 * D * (2 * M + N + L * (4 * M + 2 * N))
+                ex = {"L": L, "splits": _lib.num_splits(_lib.WS_ODE_TLM, M, N)}
+                for _ in range(3):
+                    t = timed(lambda: _lib.ode_tlm(q, p, dq, dp, 0.1, x, dx), reps=5)
+                    rep(f"TLM@{N}x{M}", t, pairs, nb, ex)
+                    t = timed(difference, reps=5)
+                    rep(f"TLM_BY_DIFFERENCE@{N}x{M}", t, 2 * pairs, 2 * L * 4 * D * (5 * M + 2 * N), {"L": L})
+                old = _lib.get_option("pk_rp")
+                try:
+                    for rp in (1, 2):
+                        _lib.set_option("pk_rp", rp)
+                        t = timed(lambda: _lib.ode_tlm(q, p, dq, dp, 0.1, x, dx), reps=5)
+                        rep(f"TLM@{N}x{M}", t, pairs, nb, dict(ex, pk_rp=rp))
+                finally:
+                    _lib.set_option("pk_rp", old)
     if args.out:
         with open(args.out, "w") as f:
             json.dump(results, f, indent=1)

@@ -25,7 +25,7 @@ KBASE, KREDSCAL, KRED, GRADK, GRADK_REV, DDK, GENDK, HESSK, LAPK, GRADLAPK, GRAD
 WS_RED, WS_ODE_SELF_FWD, WS_ODE_SELF_BWD, WS_ODE_EXT_FWD, WS_ODE_EXT_BWD, WS_GMM_ESTEP, \
     WS_GMM_MSTEP, WS_GMM_TARGETS, WS_RIDGE_CG, WS_ODE_SELF_FWD_ROWS, WS_ODE_SELF_BWD_PART, WS_GRAD, \
     WS_ODE_SELF_FWD_PHASED, WS_GMM_ASSIGN, WS_ODE_EXT_JAC, WS_ODE_EXT_INV, WS_GMM_CARRY, \
-    WS_RKHS_GRAM = range(18)
+    WS_RKHS_GRAM, WS_ODE_TLM = range(19)
 # enum dicp_grad_kind
 GRAD_HESSW, GRAD_HESSWP, GRAD_ZDOTV, GRAD_HESS3, GRAD_GRADLAP3 = range(5)
 
@@ -53,6 +53,7 @@ _SIGNATURES = {
     "dicp_lddmm_ext_jac_step_f32": [_P, _P, _I64, _P, _P, _I64, _INT, _DBL, _DBL, _DBL, _P, _P, _P, _SZ, _P],
     "dicp_lddmm_ext_inv_step_f32": [_P, _P, _P, _P, _I64, _P, _P, _I64, _INT, _DBL, _DBL, _DBL, _P, _P, _P, _SZ,
                                     _P],
+    "dicp_lddmm_ode_tlm_f32": [_P, _P, _P, _P, _I64, _P, _P, _I64, _INT, _INT, _DBL, _P, _P, _P, _P, _SZ, _P],
     "dicp_gmm_estep_f32": [_P, _I64, _P, _P, _P, _I64, _INT, _DBL, _DBL, _P, _P, _P, _P, _SZ, _P],
     "dicp_gmm_estep_hint_f32": [_P, _I64, _P, _P, _P, _I64, _INT, _DBL, _DBL, _P, _P, _P, _P, _P, _SZ, _P],
     "dicp_gmm_mstep_f32": [_P, _P, _I64, _P, _P, _I64, _INT, _DBL, _P, _P, _SZ, _P],
@@ -322,6 +323,11 @@ FLOPS_PER_PAIR = {
     # velocity gradient at carried points (csrc/ext_jac.hip), eta = 0: 3 sub + 3 fma + mul, one
     # exp2, 3 mul + 3 add + 9 fma
     "ode_ext_jac": 35,
+    # tangent-linear model of the eta = 0 ODE (csrc/tlm.hip), per self pair and direction: 6 sub +
+    # 6 fma for |z|^2 and z.dz, 2 mul, one exp2, 6 fma for dv, 9 fma for p_i.p_j and dp_i.p_j +
+    # p_i.dp_j, fma + 2 mul, 6 fma for dmG.  A carried pair costs 32 of these: ode_tlm counts it
+    # as 32 / 66 of a pair
+    "ode_tlm": 66,
 }
 # Executed fp32 arithmetic per ordered pair where it differs from the algorithmic figure
 # (FMA = 2 flop, from the hot loop's instruction counts, tools/isa_loop_stats.py): the
@@ -452,11 +458,13 @@ def _poison(ws):
     return ws
 
 
-def _workspace(kind: int, M: int, N: int, D: int, device, exclusive: bool = False):
+def _workspace(kind: int, M: int, N: int, D: int, device, exclusive: bool = False, count: int = 1):
+    """count: how many times the kind's bytes the call needs (WS_ODE_TLM: once per direction)."""
     key = (kind, int(M), int(N), int(D))
     nbytes = _WS_BYTES.get(key)
     if nbytes is None:
         nbytes = _WS_BYTES[key] = int(lib().dicp_workspace_bytes(kind, int(M), int(N), int(D)))
+    nbytes *= int(count)
     if nbytes == 0:
         return None, 0
     keep = getattr(_tl, "batch_keep", None)
@@ -875,6 +883,54 @@ def ext_inv_step(x, y, q, p, sigma: float, eta: float, dt: float, v1=None, A1=No
                                                            _stream(x.device)))
     _check_rc(rc, "ext_inv_step")
     return xn, res
+
+
+def ode_tlm(q, p, dq, dp, sigma: float, x=None, dx=None, need_self: bool = True):
+    """Tangent-linear model of the eta = 0 ODE (dicp_lddmm_ode_tlm_f32): at the support (q, p)
+    (M, D) and the carried points x (N, D) or None, along the L directions dq, dp (L, M, D) and
+    dx (L, N, D), returns (dv, dmG, dvx): the derivatives (L, M, D) of the velocity and of the
+    momentum rate of the support (None, None with need_self=False) and the derivative (L, N, D) of
+    the velocity at x (None without x).  All L directions of a part go in one launch; a
+    direction's result is bitwise independent of the others in the call."""
+    q = _dev(q, "q")
+    p = _dev(p, "p")
+    dq = _dev(dq, "dq")
+    dp = _dev(dp, "dp")
+    if q.dim() != 2 or p.shape != q.shape:
+        raise ValueError(f"ode_tlm: q and p must both be shaped (M, D), got {tuple(q.shape)} and {tuple(p.shape)}")
+    M, D = q.shape
+    if dq.dim() != 3 or tuple(dq.shape[1:]) != (M, D) or dp.shape != dq.shape:
+        raise ValueError(f"ode_tlm: dq and dp must both be shaped (L, {M}, {D}), got {tuple(dq.shape)} and "
+                         f"{tuple(dp.shape)}")
+    L = dq.shape[0]
+    if (x is None) != (dx is None):
+        raise ValueError("ode_tlm: x and dx go together")
+    N = 0
+    if x is not None:
+        x = _dev(x, "x")
+        dx = _dev(dx, "dx")
+        if x.dim() != 2 or x.shape[1] != D:
+            raise ValueError(f"ode_tlm: x must be shaped (N, {D}), got {tuple(x.shape)}")
+        N = x.shape[0]
+        if tuple(dx.shape) != (L, N, D):
+            raise ValueError(f"ode_tlm: dx must be shaped ({L}, {N}, {D}), got {tuple(dx.shape)}")
+    dev = q.device
+    if any(t is not None and t.device != dev for t in (p, dq, dp, x, dx)):
+        raise ValueError("ode_tlm: all tensors must be on the same device")
+    new = lambda rows: torch.empty((L, rows, D), device=dev, dtype=torch.float32)
+    dv, dmG = (new(M), new(M)) if need_self else (None, None)
+    dvx = None if x is None else new(N)
+    if L == 0 or (M == 0 and N == 0) or not (need_self or N):
+        return dv, dmG, dvx
+    ws, nb = _workspace(WS_ODE_TLM, M, N, D, dev, count=L)
+    pairs = L * M * ((M if need_self else 0) + N * 32 / 66)
+    nbytes = 4 * D * (2 * M + N + L * ((4 if need_self else 2) * M + 2 * N))
+    rc = _launch("ode_tlm", pairs, nbytes,
+                 lambda: lib().dicp_lddmm_ode_tlm_f32(_ptr(q), _ptr(p), _ptr(dq), _ptr(dp), M, _ptr(x), _ptr(dx), N,
+                                                      L, D, float(sigma), _ptr(dv), _ptr(dmG), _ptr(dvx), _ptr(ws),
+                                                      nb, _stream(dev)))
+    _check_rc(rc, "ode_tlm")
+    return dv, dmG, dvx
 
 
 def ode_ext_bwd(x, q, p, gvx, gdiv, sigma: float, eta: float, gq, gp):

@@ -567,6 +567,104 @@ class LDDMMModel:
                           f"within {max_iter} Newton updates per step (returned as NaN)", RuntimeWarning)
         return x0, dict(converged=converged, residual=worst, iterations=iterations, passes=passes, tol=tol)
 
+    # ------------------------------------------------------------------------------------
+    # Forward sensitivities of the shooting (extension; csrc/tlm.hip)
+    def shoot_tangent(self, q0, p0, dp0, dq0=None, x0=None, dx0=None, shoot=None, trajectory=False):
+        """The tangent-linear model of the DISCRETE flow Shoot(q0, p0, x0) computes: (dQ, dP, dX), the
+        exact first-order change of the final support points, momenta and carried points when the
+        initial ones move along dq0, dp0 (L, M, D) and dx0 (L, N, D) -- a Jacobi field along the
+        geodesic, the Gauss-Newton product J d of a data term, the sensitivity of the map to a
+        mode of the momenta.  A 2-D direction means L = 1 and is squeezed on return; dq0 = None
+        and dx0 = None mean zero; dX is None without x0.  trajectory=True: at all nt + 1 times,
+        (nt + 1, L, ., D).  The cost component gets no tangent.
+        One fused pass (_lib.ode_tlm, all L directions in one launch per part) per stage.  Euler:
+        dS <- dS + dt TLM(S_t; dS); Ralston: dk1 = TLM(S_t; dS), dk2 = TLM(S_m; dS + h dk1) at the
+        mid-state S_m = S_t + h ODE(S_t), h = 2 dt / 3, formed once per step as in flow_jacobian,
+        dS <- dS + dt/4 (dk1 + 3 dk2); the carried points are advanced the same way.
+        shoot: a forward shoot of (q0, p0) whose support states are reused (its final momenta are
+        never read); None: they are computed here.  Inputs are detached; the model (its shoot_cache
+        included) is left as it was.  With a row split the call runs replicated on every rank.
+        Only for eta = 0 (classic / hybrid): with the gradient component the field is affine in the
+        momenta, not linear, and its linearisation needs higher derivatives of the kernel.
+        ValueError then, and on directions of the wrong shape."""
+        return self._shoot_tangent(q0, p0, dp0, dq0, x0, dx0, shoot, trajectory, True)
+
+    def _shoot_tangent(self, q0, p0, dp0, dq0, x0, dx0, shoot, trajectory, need_support):
+        """shoot_tangent; need_support=False: dQ and dP at the final time are not wanted (None), so
+        the last stage runs the carried part alone."""
+        if self.eta != 0:
+            raise ValueError("shoot_tangent needs eta = 0 (gradcomponent=False): with the gradient component "
+                             "the field is affine in the momenta, not linear, and its linearisation needs "
+                             "higher derivatives of the kernel")
+        getspec(q0, p0, dp0, dq0, x0, dx0)
+        q0, p0, dp0 = q0.detach(), p0.detach(), dp0.detach()
+        single = dp0.dim() == 2
+        dp = (dp0[None] if single else dp0).contiguous()
+        if dp.dim() != 3 or tuple(dp.shape[1:]) != tuple(q0.shape) or p0.shape != q0.shape:
+            raise ValueError(f"shoot_tangent: dp0 must be shaped {tuple(q0.shape)} or (L, {q0.shape[0]}, "
+                             f"{q0.shape[1]}), got {tuple(dp0.shape)}")
+        L = dp.shape[0]
+
+        def direction(d, rows, name):
+            if d is None:
+                return torch.zeros((L,) + tuple(rows.shape), device=rows.device, dtype=rows.dtype)
+            d = d.detach()
+            d = d[None] if d.dim() == 2 else d
+            if tuple(d.shape) != (L,) + tuple(rows.shape):
+                raise ValueError(f"shoot_tangent: {name} must be shaped like its points, {tuple(rows.shape)}, "
+                                 f"with the {L} direction(s) of dp0 in front, got {tuple(d.shape)}")
+            return d.contiguous()
+
+        dq = direction(dq0, q0, "dq0")
+        if x0 is None and dx0 is not None:
+            raise ValueError("shoot_tangent: dx0 needs x0")
+        x = None if x0 is None else x0.detach().contiguous()
+        dx = None if x is None else direction(dx0, x, "dx0")
+        if shoot is None:
+            Q, P = self._support_states(q0, p0)
+        else:
+            Q, P = shoot.Q.detach(), shoot.P.detach()
+        nt = Q.shape[0] - 1
+        sigma, dt = self.Kernel.sigma, 1.0 / nt
+        h = 2 * dt / 3
+        euler = self.scheme == "Euler"
+        raw = self._raw_for(q0)
+        traj = [(dq, dp, dx)]
+        with torch.no_grad():
+            for t in range(nt):
+                q, p = Q[t], P[t]
+                last = t == nt - 1
+                if euler:
+                    dv, dmG, dvx = _lib.ode_tlm(q, p, dq, dp, sigma, x, dx, need_self=need_support or not last)
+                    if x is not None:
+                        if not last:            # the points the next step linearises at
+                            x = x + dt * _lib.ode_ext_fwd(x, q, p, sigma, 0.0, False)[0]
+                        dx = dx + dt * dvx
+                    dq, dp = (dq + dt * dv, dp + dt * dmG) if dv is not None else (None, None)
+                else:
+                    with _lib.coord_mode(raw):
+                        vq, mG = _lib.ode_self_fwd(q, p, sigma, 0.0, False)[:2]
+                    qm, pm = q + h * vq, p + h * mG
+                    dv1, dG1, dx1 = _lib.ode_tlm(q, p, dq, dp, sigma, x, dx)
+                    xm = dxm = None
+                    if x is not None:
+                        v1 = _lib.ode_ext_fwd(x, q, p, sigma, 0.0, False)[0]
+                        xm, dxm = x + h * v1, dx + h * dx1
+                    dv2, dG2, dx2 = _lib.ode_tlm(qm, pm, dq + h * dv1, dp + h * dG1, sigma, xm, dxm,
+                                                 need_self=need_support or not last)
+                    if x is not None:
+                        if not last:
+                            x = x + (dt / 4) * v1 + (3 * dt / 4) * _lib.ode_ext_fwd(xm, qm, pm, sigma, 0.0, False)[0]
+                        dx = dx + (dt / 4) * dx1 + (3 * dt / 4) * dx2
+                    dq, dp = ((dq + (dt / 4) * dv1 + (3 * dt / 4) * dv2, dp + (dt / 4) * dG1 + (3 * dt / 4) * dG2)
+                              if dv2 is not None else (None, None))
+                if trajectory:
+                    traj.append((dq, dp, dx))
+        if trajectory:
+            outs = [None if traj[-1][k] is None else torch.stack([s[k] for s in traj]) for k in range(3)]
+            return tuple(o if o is None or not single else o[:, 0] for o in outs)
+        return tuple(o if o is None or not single else o[0] for o in (dq, dp, dx))
+
     def BasicQuadLossFunctor(self, y, cmul=1):
         y = y.detach()
 

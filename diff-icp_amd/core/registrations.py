@@ -81,6 +81,22 @@ class LDDMMRegistration(Registration):
         return Q[-1], -P[-1]
 
     # ------------------------------------------------------------------------------------
+    # First-order change of the map with its momenta (extension; LDDMMModel.shoot_tangent)
+    def sensitivity(self, X, da0, dq0=None, previous_forwardshoot=None):
+        """d apply(X) along the change da0 of the initial momenta (and dq0 of the support points;
+        None: zero): (L, N, D) for da0 (L, M, D), (N, D) for a 2-D da0 -- shoot_tangent's dX with the
+        points X held fixed.  previous_forwardshoot: a forward shoot of (q0, a0) to reuse.  Only
+        for eta = 0.  Inputs are detached; nothing of the model changes."""
+        return self.LMi._shoot_tangent(self.q0, self.a0, da0, dq0, X, None, previous_forwardshoot, False,
+                                       False)[2]
+
+    def jacobi_field(self, da0, previous_forwardshoot=None):
+        """The Jacobi field along the geodesic of (q0, a0) started by the change da0 of the initial
+        momenta with the support points held fixed: (dQ, dP) at all nt + 1 times, (nt + 1, L, M, D)
+        or (nt + 1, M, D) for a 2-D da0; it starts at (0, da0).  Only for eta = 0."""
+        return self.LMi.shoot_tangent(self.q0, self.a0, da0, shoot=previous_forwardshoot, trajectory=True)[:2]
+
+    # ------------------------------------------------------------------------------------
     # Exact inverse of the map apply() computes (extension; LDDMMModel.flow_inverse)
     def inverse(self, Y, previous_forwardshoot=None, tol=None, max_iter=10, return_info=False):
         """X with apply(X) = Y: the inverse of the discrete flow itself, by Newton's iteration on

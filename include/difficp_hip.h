@@ -177,6 +177,32 @@ int dicp_lddmm_ext_inv_step_f32(const float* x, const float* y, const float* v1,
                                 double sigma, double eta, double dt, float* x_next, float* res,
                                 void* ws, size_t ws_bytes, dicp_stream_t stream);
 
+/* Tangent-linear model of the eta = 0 ODE (no reference counterpart): the exact derivative of
+ * the right-hand side at (q, p) (M, D), and of the velocity at the carried points x (N, D), along
+ * L directions dq, dp (L, M, D) and dx (L, N, D), contiguous, which share (q, p, x).  With
+ * s = 1/sigma^2, K = exp(-s |z|^2 / 2):
+ *   self rows (z = q_i - q_j, dz = dq_i - dq_j):
+ *     dv_i  = sum_j K [ dp_j - s (z.dz) p_j ]
+ *     dmG_i = s sum_j K [ (dp_i.p_j + p_i.dp_j) z + (p_i.p_j) dz - s (p_i.p_j)(z.dz) z ]
+ *   carried rows (z = x_i - q_j, dz = dx_i - dq_j):
+ *     dvx_i = sum_j K [ dp_j - s (z.dz) p_j ]
+ * into dv, dmG (L, M, D) and dvx (L, N, D).  The carried part is optional (x NULL or N = 0), and so
+ * are the self part's outputs (dv and / or dmG NULL; both NULL: that part is not run).  One pair
+ * launch per part for all L directions (the direction is a grid dimension) and, where the
+ * support is split into column chunks, one merge launch per part; no atomics.  The result of
+ * direction l is bitwise reproducible and depends on (q, p, x), that direction's (dq, dp, dx) and
+ * the sizes only -- not on L, the other directions, the device or any option but "pk_rp".
+ * Coordinates in original units; one v_exp_f32 per pair; float32 sums over 256-column tiles, then
+ * tiles, then chunks in order.  D = 2 or 3 (otherwise DICP_ERR_UNSUPPORTED).  M, N or L negative,
+ * L > 65535, sigma <= 0, a NULL pointer where data is needed, an output that is an input:
+ * DICP_ERR_INVALID, before any device work.  L = 0 launches nothing; M = 0: dvx is zeroed.
+ * Workspace kind DICP_WS_ODE_TLM: dicp_workspace_bytes answers for ONE direction, a call needs
+ * L times that.  Not batchable. */
+int dicp_lddmm_ode_tlm_f32(const float* q, const float* p, const float* dq, const float* dp,
+                           int64_t M, const float* x, const float* dx, int64_t N, int L, int D,
+                           double sigma, float* dv, float* dmG, float* dvx, void* ws,
+                           size_t ws_bytes, dicp_stream_t stream);
+
 /* VJP of the external-point terms.  Cotangents gvx (N,D) on vx and device scalar gdiv on
  * sum_i gx_i.  Writes gxo (N,D) (gradient w.r.t. x) and ACCUMULATES into gq, gp (M,D)
  * (gradient w.r.t. the support points / momenta), so it can follow the self backward. */
@@ -515,7 +541,9 @@ enum dicp_ws_kind {
   DICP_WS_ODE_EXT_INV = 15,      /* dicp_lddmm_ext_inv_step_f32: M = support points, N = carried points;
                                     the slabs of DICP_WS_ODE_EXT_JAC and N (D + D^2) floats of scratch */
   DICP_WS_GMM_CARRY = 16,        /* dicp_gmm_carry_f32: M = rows, N = columns */
-  DICP_WS_RKHS_GRAM = 17         /* dicp_rkhs_gram_f32: M = max_rows, N = npairs */
+  DICP_WS_RKHS_GRAM = 17,        /* dicp_rkhs_gram_f32: M = max_rows, N = npairs */
+  DICP_WS_ODE_TLM = 18           /* dicp_lddmm_ode_tlm_f32: M = support points, N = carried points; the
+                                    bytes of ONE direction (a call needs L times as many) */
 };
 size_t dicp_workspace_bytes(int kind, int64_t M, int64_t N, int D);
 
