@@ -4,12 +4,9 @@
 // One kernel serves both directions of the GMM match: rows = points, columns = components with
 // bias w2_c (GaussianMixtureUnif.assign), or rows = components, columns = points with bias
 // -T2_n (nearest_points; the row constant w2_c is added by the caller).
-// Structure of gmm.hip's row reductions: two rows per lane (one packed float2 pair), columns
-// staged in LDS tiles of kTile records {y, bias}, column chunks (gridDim.y) writing per-row
-// partials of K (val, idx) pairs into the workspace, merged by a second launch in chunk order.
-// No atomics.  The squared distance comes from the coordinate differences (not from the
-// |r|^2 - 2 r.y + |y|^2 expansion): a nearest-neighbour decision keeps its bits when the cloud
-// sits far from the origin.
+// The column-tile sweep of coltile.hpp over records {y, bias}; a chunk's partial is the K
+// (val, idx) pairs of each row.  The distance from coordinate differences keeps a
+// nearest-neighbour decision's bits when the cloud sits far from the origin.
 // Order (total, deterministic): larger val first; equal val: smaller column index first.  The
 // running top-K is a sorted insertion in registers that only a strictly larger val moves up, the
 // columns are visited in increasing order, and the merge pushes the chunks' lists in chunk
@@ -17,9 +14,7 @@
 // A column is returned only if its val is > -inf (a dead component, bias = -inf, never is) and
 // not NaN; slots that cannot be filled hold idx = -1, val = -inf; a row with a non-finite
 // coordinate holds idx = -1, val = NaN in every slot.
-#include "launch.hpp"
-#include "lddmm_ops.hpp"
-#include "packed.hpp"
+#include "coltile.hpp"
 
 using namespace dicp;
 
@@ -73,14 +68,6 @@ struct TopK {
   }
 };
 
-template <int D>
-__device__ __forceinline__ bool finite_row(const float* x) {
-  bool ok = true;
-#pragma unroll
-  for (int d = 0; d < D; ++d) ok = ok && (fabsf(x[d]) <= 3.4028234663852886e38f);   // NaN: false
-  return ok;
-}
-
 template <int K>
 __device__ __forceinline__ void store_final(bool finite, const TopK<K>& t, int64_t i,
                                             int32_t* __restrict__ idx, float* __restrict__ val) {
@@ -101,22 +88,15 @@ __global__ __launch_bounds__(kBlock) void assign_rowred_kernel(const float* __re
                                                                ValIdx* __restrict__ part,
                                                                int32_t* __restrict__ idx,
                                                                float* __restrict__ val) {
-  // double-buffered column tiles (as rowred_kernel): one barrier per tile
   __shared__ float4 lds[2][kTile];
-  const int tid = threadIdx.x;
-  const int64_t ibase = (int64_t)blockIdx.x * (kBlock * kAssignR) + tid;
+  const int64_t ibase = (int64_t)blockIdx.x * (kBlock * kAssignR) + threadIdx.x;
   float xr[kAssignR][D];
-#pragma unroll
-  for (int r = 0; r < kAssignR; ++r) {
-    int64_t i = ibase + (int64_t)r * kBlock;
-    if (i >= M) i = M - 1;
-    ld<D>(rows, i, xr[r]);
-  }
   f2 x[kAssignH][D];   // pair h: rows 2h (.x) and 2h + 1 (.y)
 #pragma unroll
-  for (int h = 0; h < kAssignH; ++h)
-#pragma unroll
-    for (int d = 0; d < D; ++d) x[h][d] = f2{xr[2 * h][d], xr[2 * h + 1][d]};
+  for (int h = 0; h < kAssignH; ++h) {
+    const int64_t i0 = ibase + (int64_t)(2 * h) * kBlock;
+    load_row_pair<D>(rows, M, i0, i0 + kBlock, xr[2 * h], xr[2 * h + 1], x[h]);
+  }
   const f2 nc2 = splat(nc);
   TopK<K> top[kAssignR];
 #pragma unroll
@@ -126,29 +106,25 @@ __global__ __launch_bounds__(kBlock) void assign_rowred_kernel(const float* __re
   int64_t j1 = j0 + chunk;
   if (j1 > N) j1 = N;
 
-  auto stage = [&](int buf, int64_t j) {
-    float y[D];
-    ld<D>(cols, j, y);
-    const float b = bias ? bias[j] : 0.f;
-    lds[buf][tid] = D == 2 ? make_float4(y[0], y[1], b, 0.f) : make_float4(y[0], y[1], y[D - 1], b);
+  auto stage = [&](int buf, int64_t j, int cnt) {
+    const int tid = threadIdx.x;   // read here: captured by reference it costs two VGPRs
+    if (tid < cnt) {
+      float y[D];
+      ld<D>(cols, j + tid, y);
+      const float b = bias ? bias[j + tid] : 0.f;
+      lds[buf][tid] = BiasCol::pack<D>(y, b);
+    }
   };
-  int cnt = j0 < j1 ? (int)((j1 - j0) < kTile ? (j1 - j0) : kTile) : 0;
-  if (tid < cnt) stage(0, j0 + tid);
-  __syncthreads();
-  int buf = 0;
-  for (int64_t jt = j0; jt < j1; jt += kTile) {
-    const int64_t jn = jt + kTile;
-    const int cntn = jn < j1 ? (int)((j1 - jn) < kTile ? (j1 - jn) : kTile) : 0;
-    if (tid < cntn) stage(buf ^ 1, jn + tid);
-    const float4* tile = lds[buf];
-    const int jb = (int)jt;   // N < 2^31 (checked by the entry)
+  for (ColTiles ts(j0, j1, stage); ts.begin_tile(); ts.end_tile()) {
+    const float4* tile = lds[ts.buf];
+    const int jb = (int)ts.jt;   // N < 2^31 (checked by the entry)
 #pragma unroll 2
-    for (int t = 0; t < cnt; ++t) {
-      const float4 q = tile[t];
-      const float y[3] = {q.x, q.y, q.z};
-      const float b = D == 2 ? q.z : q.w;
+    for (int t = 0; t < ts.cnt; ++t) {
+      float y[3], b;
+      BiasCol::unpack<D>(tile[t], y, b);
 #pragma unroll
       for (int h = 0; h < kAssignH; ++h) {
+        // pk_sqdist written out: through the helper <3, 1> takes one VGPR more
         f2 z = x[h][0] - splat(y[0]);
         f2 d2 = z * z;
 #pragma unroll
@@ -161,9 +137,6 @@ __global__ __launch_bounds__(kBlock) void assign_rowred_kernel(const float* __re
         top[2 * h + 1].push(v.y, jb + t);
       }
     }
-    __syncthreads();
-    buf ^= 1;
-    cnt = cntn;
   }
 
 #pragma unroll
@@ -213,10 +186,7 @@ __global__ __launch_bounds__(kBlock) void assign_merge_kernel(const ValIdx* __re
 int assign_splits(int64_t M, int64_t N) {
   static int64_t cap = -1;
   if (cap < 0) cap = (int64_t)device_cus() * blocks_per_cu(assign_rowred_kernel<3, kAssignMaxK>);
-  const int S = num_splits_cap(M, N, kAssignR, cap, 32000, 3);
-  if (S <= kAssignMaxSplits) return S;
-  const int64_t chunk = round_chunk(N, kAssignMaxSplits);
-  return (int)((N + chunk - 1) / chunk);
+  return splits_capped(M, N, kAssignR, cap, 32000, 3, kAssignMaxSplits);
 }
 
 size_t assign_ws_bytes(int64_t M, int64_t N, int K) {
@@ -228,27 +198,17 @@ size_t assign_ws_bytes(int64_t M, int64_t N, int K) {
 template <int D, int K>
 int launch_assign(const float* rows, int64_t M, const float* cols, const float* bias, int64_t N,
                   double sigma, int32_t* idx, float* val, void* ws, size_t ws_bytes, hipStream_t st) {
-  const int64_t nb = (M + kBlock - 1) / kBlock;
-  if (N == 0) {
-    assign_merge_kernel<D, K><<<dim3((unsigned)nb), dim3(kBlock), 0, st>>>(nullptr, M, 0, rows, idx, val);
-    return check_launch("gmm_assign");
-  }
-  const int S = assign_splits(M, N);
-  const int64_t chunk = chunk_of(N, S);
-  const int64_t bx = (M + (int64_t)kBlock * kAssignR - 1) / ((int64_t)kBlock * kAssignR);
-  const size_t need = assign_ws_bytes(M, N, K);
-  if (need > 0 && (ws == nullptr || ws_bytes < need)) {
-    set_error("gmm_assign: workspace too small (%zu < %zu bytes)", ws_bytes, need);
-    return DICP_ERR_WORKSPACE;
-  }
+  if (int rc = check_ws("gmm_assign", ws, ws_bytes, assign_ws_bytes(M, N, K))) return rc;
+  const int S = N > 0 ? assign_splits(M, N) : 0;
+  const int64_t chunk = S > 0 ? chunk_of(N, S) : 0;
   const float nc = make_scal(sigma, 0.0).nc;
   ValIdx* part = S > 1 ? reinterpret_cast<ValIdx*>(ws) : nullptr;
-  assign_rowred_kernel<D, K><<<dim3((unsigned)bx, (unsigned)S), dim3(kBlock), 0, st>>>(
-      rows, M, cols, bias, N, nc, chunk, part, idx, val);
-  int rc = check_launch("gmm_assign");
-  if (rc || S == 1) return rc;
-  assign_merge_kernel<D, K><<<dim3((unsigned)nb), dim3(kBlock), 0, st>>>(part, M, S, rows, idx, val);
-  return check_launch("gmm_assign");
+  return launch_chunked(
+      "gmm_assign", (M + kBlock - 1) / kBlock, (M + kBlock * kAssignR - 1) / (kBlock * kAssignR), S,
+      [&](dim3 grid) {
+        assign_rowred_kernel<D, K><<<grid, dim3(kBlock), 0, st>>>(rows, M, cols, bias, N, nc, chunk, part, idx, val);
+      },
+      [&](dim3 grid) { assign_merge_kernel<D, K><<<grid, dim3(kBlock), 0, st>>>(part, M, S, rows, idx, val); });
 }
 
 template <int D>

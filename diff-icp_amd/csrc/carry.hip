@@ -8,11 +8,9 @@
 // bias w2_c and component attributes (GaussianMixtureUnif.carry_to_points), or rows =
 // components, columns = points with bias -T2_n + log2 (1 - gamma0_n) and a per-point field
 // (pool_from_points).
-// Structure of assign.hip: two rows per lane (one packed float2 pair), columns staged in
-// double-buffered LDS tiles of kTile records {y, bias} + FB feature channels, column chunks
-// (gridDim.y) writing per-row partials (m, l, acc[FB]) into the workspace, merged by a second
-// launch in chunk order.  No atomics.  The squared distance comes from the coordinate
-// differences.  Channels go in blocks of FB in {1, 4, 8, 16} (<= kCarryMaxF), one pass per block
+// The column-tile sweep of coltile.hpp over records {y, bias} + FB feature channels; a chunk's
+// partial is (m, l, acc[FB]) of each row.
+// Channels go in blocks of FB in {1, 4, 8, 16} (<= kCarryMaxF), one pass per block
 // on the same stream; every block forms bitwise the same weights, so a channel's result does not
 // depend on which block, or which F, it is computed in.
 // Shift rule (no shift comes from the caller).  Each row carries a reference m_i, an integer
@@ -30,9 +28,7 @@
 // staging (0 * NaN would be NaN).  No live column (N = 0 or all dead): lse2 = -inf, out = NaN.
 // A row with a non-finite coordinate: lse2 = NaN, out = NaN.  A non-finite feature in a live
 // column makes its channel non-finite in every row (no skipping by weight).
-#include "launch.hpp"
-#include "lddmm_ops.hpp"
-#include "packed.hpp"
+#include "coltile.hpp"
 
 using namespace dicp;
 
@@ -44,14 +40,6 @@ constexpr int kCarryR = 2;            // rows per lane: one packed pair
 constexpr int kCarryMaxSplits = 256;
 constexpr float kCarryNoRef = -3.4028234663852886e38f;   // m of a row that met no live column
 constexpr float kCarryMove = 1.152921504606846976e18f;   // 2^60: a tile sum that moves m
-
-template <int D>
-__device__ __forceinline__ bool finite_row(const float* x) {
-  bool ok = true;
-#pragma unroll
-  for (int d = 0; d < D; ++d) ok = ok && (fabsf(x[d]) <= 3.4028234663852886e38f);   // NaN: false
-  return ok;
-}
 
 // part: slab (s, k) of M floats at part[((int64_t)s * (FB + 2) + k) * M], k = 0: m, 1: l, 2 + f: acc_f
 template <int FB>
@@ -76,21 +64,13 @@ __global__ __launch_bounds__(kBlock) void carry_rowred_kernel(const float* __res
                                                               float* __restrict__ part,
                                                               float* __restrict__ out,
                                                               float* __restrict__ lse2) {
-  // double-buffered column tiles (as rowred_kernel): one barrier per tile
   __shared__ float4 lds[2][kTile];
   __shared__ __attribute__((aligned(16))) float ldf[2][kTile * FB];
   const int tid = threadIdx.x;
   const int64_t ibase = (int64_t)blockIdx.x * (kBlock * kCarryR) + tid;
   float xr[kCarryR][D];
-#pragma unroll
-  for (int r = 0; r < kCarryR; ++r) {
-    int64_t i = ibase + (int64_t)r * kBlock;
-    if (i >= M) i = M - 1;
-    ld<D>(rows, i, xr[r]);
-  }
   f2 x[D];   // rows ibase (.x) and ibase + kBlock (.y)
-#pragma unroll
-  for (int d = 0; d < D; ++d) x[d] = f2{xr[0][d], xr[1][d]};
+  load_row_pair<D>(rows, M, ibase, ibase + kBlock, xr[0], xr[1], x);
   const f2 nc2 = splat(nc);
 
   const int64_t j0 = (int64_t)blockIdx.y * chunk;
@@ -102,7 +82,7 @@ __global__ __launch_bounds__(kBlock) void carry_rowred_kernel(const float* __res
       float y[D];
       ld<D>(cols, j + tid, y);
       const float b = bias ? bias[j + tid] : 0.f;
-      lds[buf][tid] = D == 2 ? make_float4(y[0], y[1], b, 0.f) : make_float4(y[0], y[1], y[D - 1], b);
+      lds[buf][tid] = BiasCol::pack<D>(y, b);
     }
     for (int e = tid; e < cnt * FB; e += kBlock) {
       const int t = e / FB, c = e % FB;
@@ -111,16 +91,9 @@ __global__ __launch_bounds__(kBlock) void carry_rowred_kernel(const float* __res
     }
   };
   auto logit = [&](const float4 q) {
-    const float y[3] = {q.x, q.y, q.z};
-    const float b = D == 2 ? q.z : q.w;
-    f2 z = x[0] - splat(y[0]);
-    f2 d2 = z * z;
-#pragma unroll
-    for (int d = 1; d < D; ++d) {
-      z = x[d] - splat(y[d]);
-      d2 = pk_fma(z, z, d2);
-    }
-    return pk_fma(nc2, d2, splat(b));
+    float y[3], b;
+    BiasCol::unpack<D>(q, y, b);
+    return pk_fma(nc2, pk_sqdist<D>(x, y), splat(b));
   };
   // floor of the tile's largest logit per row (-inf without a live column; NaN logits pass by)
   auto tile_max = [&](const float4* tile, int cnt) {
@@ -138,6 +111,9 @@ __global__ __launch_bounds__(kBlock) void carry_rowred_kernel(const float* __res
 #pragma unroll
   for (int f = 0; f < FB; ++f) tot[f] = splat(0.f);
 
+  // The sweep of coltile.hpp written out, with the reference pass over the chunk's first tile
+  // after the first barrier: under the ColTiles loop header the staging code around the loop
+  // compiles differently (2 VGPRs more at D = 3, FB = 1; 1 % slower at 10 tiles per chunk)
   int cnt = j0 < j1 ? (int)((j1 - j0) < kTile ? (j1 - j0) : kTile) : 0;
   stage(0, j0, cnt);
   __syncthreads();
@@ -254,10 +230,7 @@ __global__ __launch_bounds__(kBlock) void carry_merge_kernel(const float* __rest
 int carry_splits(int64_t M, int64_t N) {
   static int64_t cap = -1;
   if (cap < 0) cap = (int64_t)device_cus() * blocks_per_cu(carry_rowred_kernel<3, kCarryMaxF>);
-  const int S = num_splits_cap(M, N, kCarryR, cap, 11000, 9);
-  if (S <= kCarryMaxSplits) return S;
-  const int64_t chunk = round_chunk(N, kCarryMaxSplits);
-  return (int)((N + chunk - 1) / chunk);
+  return splits_capped(M, N, kCarryR, cap, 11000, 9, kCarryMaxSplits);
 }
 
 // sized for one channel block of kCarryMaxF: (m, l, acc[16]) per chunk and row
@@ -271,32 +244,24 @@ template <int D, int FB>
 int launch_carry(const float* rows, int64_t M, const float* cols, const float* bias, const float* feat,
                  int64_t N, int F, int f0, int fw, float nc, int S, float* out, float* lse2, float* part,
                  hipStream_t st) {
-  const int64_t nb = (M + kBlock - 1) / kBlock;
-  if (N == 0) {
-    carry_merge_kernel<D, FB><<<dim3((unsigned)nb), dim3(kBlock), 0, st>>>(nullptr, M, 0, rows, F, f0, fw,
-                                                                           out, lse2);
-    return check_launch("gmm_carry");
-  }
-  const int64_t chunk = chunk_of(N, S);
-  const int64_t bx = (M + (int64_t)kBlock * kCarryR - 1) / ((int64_t)kBlock * kCarryR);
-  carry_rowred_kernel<D, FB><<<dim3((unsigned)bx, (unsigned)S), dim3(kBlock), 0, st>>>(
-      rows, M, cols, bias, feat, N, F, f0, fw, nc, chunk, S > 1 ? part : nullptr, out, lse2);
-  int rc = check_launch("gmm_carry");
-  if (rc || S == 1) return rc;
-  carry_merge_kernel<D, FB><<<dim3((unsigned)nb), dim3(kBlock), 0, st>>>(part, M, S, rows, F, f0, fw, out,
-                                                                         lse2);
-  return check_launch("gmm_carry");
+  const int64_t chunk = S > 0 ? chunk_of(N, S) : 0;
+  if (S <= 1) part = nullptr;
+  return launch_chunked(
+      "gmm_carry", (M + kBlock - 1) / kBlock, (M + kBlock * kCarryR - 1) / (kBlock * kCarryR), S,
+      [&](dim3 grid) {
+        carry_rowred_kernel<D, FB><<<grid, dim3(kBlock), 0, st>>>(rows, M, cols, bias, feat, N, F, f0, fw, nc,
+                                                                  chunk, part, out, lse2);
+      },
+      [&](dim3 grid) {
+        carry_merge_kernel<D, FB><<<grid, dim3(kBlock), 0, st>>>(part, M, S, rows, F, f0, fw, out, lse2);
+      });
 }
 
 template <int D>
 int carry_d(const float* rows, int64_t M, const float* cols, const float* bias, const float* feat, int64_t N,
             int F, double sigma, float* out, float* lse2, void* ws, size_t ws_bytes, hipStream_t st) {
-  const int S = N > 0 ? carry_splits(M, N) : 1;
-  const size_t need = N > 0 ? carry_ws_bytes(M, N) : 0;
-  if (need > 0 && (ws == nullptr || ws_bytes < need)) {
-    set_error("gmm_carry: workspace too small (%zu < %zu bytes)", ws_bytes, need);
-    return DICP_ERR_WORKSPACE;
-  }
+  const int S = N > 0 ? carry_splits(M, N) : 0;   // 0: no columns, the merge alone
+  if (int rc = check_ws("gmm_carry", ws, ws_bytes, carry_ws_bytes(M, N))) return rc;
   const float nc = make_scal(sigma, 0.0).nc;
   float* part = reinterpret_cast<float*>(ws);
   // channel blocks one after the other on the stream: each reuses the workspace

@@ -3,9 +3,8 @@
 //   out[n] = sum_{i in a} sum_{j in b} (p_i . p_j) exp(-|q_i - q_j|^2 / (2 sigma^2)),
 // the inner product <v_a, v_b>_V of the eta = 0 velocity fields -- the input of tangent-space
 // statistics of an atlas (core/statistics.py).  One scalar per pair, in float64.
-// Structure of carry.hip: two rows per lane (one packed float2 pair), the columns of field b
-// staged in double-buffered LDS tiles of kTile records {q, p}, the squared distance from the
-// coordinate differences, the exponent in the log2 domain with one v_exp_f32 per pair term.
+// The column-tile sweep of coltile.hpp over the records {q, p} of field b, the exponent in the
+// log2 domain with one v_exp_f32 per pair term.
 // The grid is (pair, row block of a, column chunk of b): every workgroup sums its kBlock *
 // kGramR rows x kGramChunk columns and writes ONE double into its own workspace slot; a
 // second launch adds each pair's slots in a fixed order.  No atomics.
@@ -21,9 +20,7 @@
 // Non-finite input: a point with a non-finite coordinate has its momentum replaced by NaN (an
 // infinite distance alone would give weight 0 and hide it), so every pair that contains the
 // field and whose other field is not empty is non-finite; no other pair reads the point.
-#include "launch.hpp"
-#include "lddmm_ops.hpp"
-#include "packed.hpp"
+#include "coltile.hpp"
 
 using namespace dicp;
 
@@ -33,14 +30,6 @@ constexpr int kGramR = 2;                       // rows per lane: one packed pai
 constexpr int64_t kGramRows = kBlock * kGramR;  // rows per workgroup
 constexpr int64_t kGramChunk = 8 * kTile;       // columns per workgroup (a whole number of tiles)
 constexpr int64_t kGramMaxRows = 65535 * kGramRows;   // gridDim.y (and .z, the longer extent)
-
-template <int D>
-__device__ __forceinline__ bool gram_finite(const float* x) {
-  bool ok = true;
-#pragma unroll
-  for (int d = 0; d < D; ++d) ok = ok && (fabsf(x[d]) <= 3.4028234663852886e38f);   // NaN: false
-  return ok;
-}
 
 // workgroup total of one double per lane, in a fixed tree; valid in thread 0
 __device__ __forceinline__ double block_sum(double v, double* red) {
@@ -62,7 +51,6 @@ __global__ __launch_bounds__(kBlock) void gram_pair_kernel(const float* __restri
                                                            const int64_t* __restrict__ offsets,
                                                            const int32_t* __restrict__ pairs, float nc,
                                                            double* __restrict__ part) {
-  // double-buffered column tiles (as carry_rowred_kernel): one barrier per tile
   __shared__ float4 lq[2][kTile];                   // D = 2: {q, p};  D = 3: {q, p_0}
   __shared__ float2 lp[2][D == 3 ? kTile : 1];      // D = 3: {p_1, p_2}
   __shared__ double red[kBlock];
@@ -89,7 +77,7 @@ __global__ __launch_bounds__(kBlock) void gram_pair_kernel(const float* __restri
     if (i < Ma) {
       ld<D>(q, oa + i, xr[r]);
       ld<D>(p, oa + i, pr[r]);
-      if (!gram_finite<D>(xr[r])) {
+      if (!finite_row<D>(xr[r])) {
 #pragma unroll
         for (int d = 0; d < D; ++d) pr[r][d] = nan;
       }
@@ -111,7 +99,7 @@ __global__ __launch_bounds__(kBlock) void gram_pair_kernel(const float* __restri
       float y[D], pj[D];
       ld<D>(q, ob + j + tid, y);
       ld<D>(p, ob + j + tid, pj);
-      if (!gram_finite<D>(y)) {
+      if (!finite_row<D>(y)) {
 #pragma unroll
         for (int d = 0; d < D; ++d) pj[d] = nan;
       }
@@ -125,19 +113,12 @@ __global__ __launch_bounds__(kBlock) void gram_pair_kernel(const float* __restri
   };
 
   double tot = 0.0;
-  int cnt = (int)((j1 - j0) < kTile ? (j1 - j0) : kTile);
-  stage(0, j0, cnt);
-  __syncthreads();
-  int buf = 0;
-  for (int64_t jt = j0; jt < j1; jt += kTile) {
-    const int64_t jn = jt + kTile;
-    const int cntn = jn < j1 ? (int)((j1 - jn) < kTile ? (j1 - jn) : kTile) : 0;
-    stage(buf ^ 1, jn, cntn);
-    const float4* tq = lq[buf];
-    const float2* tp = lp[buf];
+  for (ColTiles ts(j0, j1, stage); ts.begin_tile(); ts.end_tile()) {
+    const float4* tq = lq[ts.buf];
+    const float2* tp = lp[ts.buf];
     f2 acc = splat(0.f);
 #pragma unroll 2
-    for (int t = 0; t < cnt; ++t) {
+    for (int t = 0; t < ts.cnt; ++t) {
       const float4 c = tq[t];
       float y[3], pj[3];
       y[0] = c.x, y[1] = c.y;
@@ -147,24 +128,15 @@ __global__ __launch_bounds__(kBlock) void gram_pair_kernel(const float* __restri
         const float2 e = tp[t];
         y[2] = c.z, pj[0] = c.w, pj[1] = e.x, pj[2] = e.y;
       }
-      f2 z = x[0] - splat(y[0]);
-      f2 d2 = z * z;
       f2 dot = pi[0] * splat(pj[0]);
 #pragma unroll
-      for (int d = 1; d < D; ++d) {
-        z = x[d] - splat(y[d]);
-        d2 = pk_fma(z, z, d2);
-        dot = pk_fma(pi[d], splat(pj[d]), dot);
-      }
-      const f2 e = nc2 * d2;
+      for (int d = 1; d < D; ++d) dot = pk_fma(pi[d], splat(pj[d]), dot);
+      const f2 e = nc2 * pk_sqdist<D>(x, y);
       const f2 k = f2{fast_exp2(e.x), fast_exp2(e.y)};
       acc = pk_fma(dot, k, acc);
     }
     tot += (double)acc.x;
     tot += (double)acc.y;
-    __syncthreads();
-    buf ^= 1;
-    cnt = cntn;
   }
   const double s = block_sum(tot, red);
   if (tid == 0) part[slot] = s;
@@ -207,10 +179,7 @@ extern "C" int dicp_rkhs_gram_f32(const float* q, const float* p, const int64_t*
     set_error("dicp_rkhs_gram_f32: invalid arguments (a null pointer, or sigma <= 0)");
     return DICP_ERR_INVALID;
   }
-  if (ws_bytes < need) {
-    set_error("rkhs_gram: workspace too small (%zu < %zu bytes)", ws_bytes, need);
-    return DICP_ERR_WORKSPACE;
-  }
+  if (int rc = check_ws("rkhs_gram", ws, ws_bytes, need)) return rc;
   if (int rc = no_batch("rkhs_gram")) return rc;
   double* part = reinterpret_cast<double*>(ws);
   const int64_t by = gram_row_blocks(max_rows), bz = gram_chunks(max_rows);
