@@ -42,6 +42,8 @@ FLOPS_PER_PAIR = {
     # tangent-linear pass (csrc/tlm.hip): 66 per self pair and 32 per carried pair, M = N: 49 on
     # average; the central difference pays 2 x (33 + 22) per such pair of pairs
     "TLM": 49, "TLM_BY_DIFFERENCE": 55,
+    # second-order pass (csrc/hvp.hip), without and with the cost terms; the VJP beside it
+    "HVP": 133, "HVP_COST": 194, "HVP_VJP": 80,
 }
 # HBM bytes per launch (algorithmic: each input read once, each output written once).
 
@@ -299,6 +301,25 @@ def main():
                         rep(f"TLM@{N}x{M}", t, pairs, nb, dict(ex, pk_rp=rp))
                 finally:
                     _lib.set_option("pk_rp", old)
+    if only is None or "HVP" in only:
+        # one second-order pass (csrc/hvp.hip) for L directions, without and with the cost terms,
+        # next to the L VJPs a stage of LDDMMModel.loss_hvp runs beside it; alternated three times
+        for M in ([20000] if args.quick else [20000, 100000]):
+            q, p = torch.rand(M, D, device=dev), 0.01 * torch.randn(M, D, device=dev)
+            aq, ap = 0.1 * torch.randn(M, D, device=dev), 0.01 * torch.randn(M, D, device=dev)
+            g = torch.ones(1, device=dev)
+            for L in (1, 4):
+                bq, bp = 0.1 * torch.randn(L, M, D, device=dev), 0.01 * torch.randn(L, M, D, device=dev)
+                nb = 4 * D * M * (4 + 4 * L)
+                ex = {"L": L, "splits": _lib.num_splits(_lib.WS_ODE_HVP, M, M)}
+                for _ in range(3):
+                    t = timed(lambda: _lib.ode_hvp(q, p, aq, ap, bq, bp, 0.1), reps=5)
+                    rep(f"HVP@{M}x{M}", t, L * M * M, nb, ex)
+                    t = timed(lambda: _lib.ode_hvp(q, p, aq, ap, bq, bp, 0.1, g), reps=5)
+                    rep(f"HVP_COST@{M}x{M}", t, L * M * M, nb, ex)
+                    t = timed(lambda: [_lib.ode_self_bwd(q, p, bq[l], bp[l], None, 0.1, 0.0) for l in range(L)],
+                              reps=5)
+                    rep(f"HVP_VJP@{M}x{M}", t, L * M * M, L * 4 * M * 6 * D, {"L": L})
     if args.out:
         with open(args.out, "w") as f:
             json.dump(results, f, indent=1)

@@ -25,7 +25,7 @@ KBASE, KREDSCAL, KRED, GRADK, GRADK_REV, DDK, GENDK, HESSK, LAPK, GRADLAPK, GRAD
 WS_RED, WS_ODE_SELF_FWD, WS_ODE_SELF_BWD, WS_ODE_EXT_FWD, WS_ODE_EXT_BWD, WS_GMM_ESTEP, \
     WS_GMM_MSTEP, WS_GMM_TARGETS, WS_RIDGE_CG, WS_ODE_SELF_FWD_ROWS, WS_ODE_SELF_BWD_PART, WS_GRAD, \
     WS_ODE_SELF_FWD_PHASED, WS_GMM_ASSIGN, WS_ODE_EXT_JAC, WS_ODE_EXT_INV, WS_GMM_CARRY, \
-    WS_RKHS_GRAM, WS_ODE_TLM = range(19)
+    WS_RKHS_GRAM, WS_ODE_TLM, WS_ODE_HVP = range(20)
 # enum dicp_grad_kind
 GRAD_HESSW, GRAD_HESSWP, GRAD_ZDOTV, GRAD_HESS3, GRAD_GRADLAP3 = range(5)
 
@@ -54,6 +54,7 @@ _SIGNATURES = {
     "dicp_lddmm_ext_inv_step_f32": [_P, _P, _P, _P, _I64, _P, _P, _I64, _INT, _DBL, _DBL, _DBL, _P, _P, _P, _SZ,
                                     _P],
     "dicp_lddmm_ode_tlm_f32": [_P, _P, _P, _P, _I64, _P, _P, _I64, _INT, _INT, _DBL, _P, _P, _P, _P, _SZ, _P],
+    "dicp_lddmm_ode_hvp_f32": [_P, _P, _P, _P, _P, _P, _I64, _INT, _INT, _DBL, _P, _P, _P, _P, _SZ, _P],
     "dicp_gmm_estep_f32": [_P, _I64, _P, _P, _P, _I64, _INT, _DBL, _DBL, _P, _P, _P, _P, _SZ, _P],
     "dicp_gmm_estep_hint_f32": [_P, _I64, _P, _P, _P, _I64, _INT, _DBL, _DBL, _P, _P, _P, _P, _P, _SZ, _P],
     "dicp_gmm_mstep_f32": [_P, _P, _I64, _P, _P, _I64, _INT, _DBL, _P, _P, _SZ, _P],
@@ -328,6 +329,13 @@ FLOPS_PER_PAIR = {
     # p_i.dp_j, fma + 2 mul, 6 fma for dmG.  A carried pair costs 32 of these: ode_tlm counts it
     # as 32 / 66 of a pair
     "ode_tlm": 66,
+    # second-order operator of the eta = 0 ODE (csrc/hvp.hip), per pair and direction, from the pair
+    # body: 9 sub + 12 fma for z, alpha, beta and their four dot products, 4 mul + fma for K's
+    # exponent and A, one exp2, 21 fma for the four momentum products, 3 mul + 9 fma for out_p,
+    # 5 fma + 3 mul for the three out_q coefficients, 9 fma for out_q (76 packed instructions per
+    # row pair).  The cost terms (gdiv) add 37: 7 sub, 5 mul and 25 fma, 61 flop ("ode_hvp_cost")
+    "ode_hvp": 133,
+    "ode_hvp_cost": 194,
 }
 # Executed fp32 arithmetic per ordered pair where it differs from the algorithmic figure
 # (FMA = 2 flop, from the hot loop's instruction counts, tools/isa_loop_stats.py): the
@@ -931,6 +939,48 @@ def ode_tlm(q, p, dq, dp, sigma: float, x=None, dx=None, need_self: bool = True)
                                                       nb, _stream(dev)))
     _check_rc(rc, "ode_tlm")
     return dv, dmG, dvx
+
+
+def ode_hvp(q, p, aq, ap, bq, bp, sigma: float, gdiv=None):
+    """Second-order operator of the eta = 0 ODE (dicp_lddmm_ode_hvp_f32): at the support (q, p)
+    (M, D), for the shared direction (aq, ap) (M, D) and the L directions bq, bp (L, M, D), returns
+    (out_q, out_p) (L, M, D) = T(S; a, b_l) + gdiv D^2 C(S) b_l.  gdiv: None (the cost terms are
+    not evaluated) or a device tensor with one element, as in ode_self_bwd.  All L directions go
+    in one launch; a direction's result is bitwise independent of the others in the call."""
+    q = _dev(q, "q")
+    p = _dev(p, "p")
+    aq = _dev(aq, "aq")
+    ap = _dev(ap, "ap")
+    bq = _dev(bq, "bq")
+    bp = _dev(bp, "bp")
+    if q.dim() != 2 or p.shape != q.shape:
+        raise ValueError(f"ode_hvp: q and p must both be shaped (M, D), got {tuple(q.shape)} and {tuple(p.shape)}")
+    M, D = q.shape
+    if aq.shape != q.shape or ap.shape != q.shape:
+        raise ValueError(f"ode_hvp: aq and ap must both be shaped ({M}, {D}), got {tuple(aq.shape)} and "
+                         f"{tuple(ap.shape)}")
+    if bq.dim() != 3 or tuple(bq.shape[1:]) != (M, D) or bp.shape != bq.shape:
+        raise ValueError(f"ode_hvp: bq and bp must both be shaped (L, {M}, {D}), got {tuple(bq.shape)} and "
+                         f"{tuple(bp.shape)}")
+    L = bq.shape[0]
+    dev = q.device
+    if gdiv is not None:
+        if gdiv.numel() != 1:
+            raise ValueError(f"ode_hvp: gdiv must be shaped (1,), got {tuple(gdiv.shape)}")
+        gdiv = _dev(gdiv.reshape(-1)[:1], "gdiv")
+    if any(t is not None and t.device != dev for t in (p, aq, ap, bq, bp, gdiv)):
+        raise ValueError("ode_hvp: all tensors must be on the same device")
+    out_q = torch.empty((L, M, D), device=dev, dtype=torch.float32)
+    out_p = torch.empty((L, M, D), device=dev, dtype=torch.float32)
+    if L == 0 or M == 0:
+        return out_q, out_p
+    ws, nb = _workspace(WS_ODE_HVP, M, M, D, dev, count=L)
+    rc = _launch("ode_hvp" if gdiv is None else "ode_hvp_cost", L * M * M, 4 * D * M * (4 + 4 * L),
+                 lambda: lib().dicp_lddmm_ode_hvp_f32(_ptr(q), _ptr(p), _ptr(aq), _ptr(ap), _ptr(bq), _ptr(bp), M,
+                                                      L, D, float(sigma), _ptr(gdiv), _ptr(out_q), _ptr(out_p),
+                                                      _ptr(ws), nb, _stream(dev)))
+    _check_rc(rc, "ode_hvp")
+    return out_q, out_p
 
 
 def ode_ext_bwd(x, q, p, gvx, gdiv, sigma: float, eta: float, gq, gp):

@@ -159,6 +159,31 @@ for _m in ("append", "extend", "insert", "pop", "remove", "sort", "reverse", "cl
 del _m
 
 
+def _data_grad(dataloss, x):
+    """grad dataloss(x) by autograd (zeros where the loss does not read x)."""
+    with torch.enable_grad():
+        x = x.detach().requires_grad_(True)
+        val = dataloss(x).sum()
+        g = torch.autograd.grad(val, x, allow_unused=True)[0] if val.requires_grad else None
+    return torch.zeros_like(x) if g is None else g.detach()
+
+
+def _autograd_data_hvp(dataloss, x, dx):
+    """(Hess dataloss)(x) dx_l for the directions dx (L, ...) by torch double-backward, one
+    direction at a time (zeros where the gradient does not depend on x)."""
+    outs = []
+    for l in range(dx.shape[0]):
+        with torch.enable_grad():
+            xr = x.detach().requires_grad_(True)
+            val = dataloss(xr).sum()
+            g = torch.autograd.grad(val, xr, create_graph=True, allow_unused=True)[0] if val.requires_grad else None
+            hv = None
+            if g is not None and g.requires_grad:
+                hv = torch.autograd.grad(g, xr, dx[l], allow_unused=True)[0]
+        outs.append(torch.zeros_like(x) if hv is None else hv.detach())
+    return torch.stack(outs) if outs else dx.clone()
+
+
 class LDDMMModel:
 
     def __init__(self, sigma=1.0, D=2, lambd=2.0, spec=defspec, gradcomponent=True,
@@ -665,11 +690,149 @@ class LDDMMModel:
             return tuple(o if o is None or not single else o[:, 0] for o in outs)
         return tuple(o if o is None or not single else o[0] for o in (dq, dp, dx))
 
+    # ------------------------------------------------------------------------------------
+    # Hessian-vector products of the shooting loss (extension; csrc/hvp.hip)
+    def loss_hvp(self, dataloss, q0, p0, d, data_hvp=None, gauss_newton=False, shoot=None):
+        """The Hessian-vector product of the loss Optimize minimises without carried points,
+        L(p0) = lam H(q0, p0) + cost_nt + dataloss(q_nt), along d, shaped like d: (M, D), or
+        (L, M, D) for L directions at once -- the exact second derivative of the DISCRETE Euler /
+        Ralston shooting by its second-order adjoint.  With VJP = DF^T (_lib.ode_self_bwd), TLM = DF
+        (_lib.ode_tlm), u(l) = (-l_p, l_q), T the third-derivative operator of the Hamiltonian and
+        C the divergence sum of the hybrid model's cost channel (_lib.ode_hvp; gam = 1 with the
+        log-determinant, else 0), Euler:
+          dS_0 = (0, d),  dS_t+1 = dS_t + dt TLM(S_t; dS_t)                  (_shoot_tangent)
+          l_nt = (grad data, 0),  l_t = l_t+1 + dt [VJP(S_t; l_t+1) + gam grad C(S_t)]
+          dl_nt = (Hess data dq_nt, 0),
+          dl_t = dl_t+1 + dt [VJP(S_t; dl_t+1) + T(S_t; u(l_t+1), dS_t) + gam D^2 C(S_t) dS_t]
+          Hess L d = (dl_0)_p + lam K(q0, q0) d;
+        Ralston (h = 2 dt / 3, S_m = S + h F(S), dS_m = dS + h TLM(S; dS), l', dl' incoming):
+          m = 3dt/4 [VJP(S_m; l') + gam grad C(S_m)],  c = dt/4 l' + h m,
+          l = l' + m + VJP(S; c) + dt/4 gam grad C(S)
+          dm = 3dt/4 [VJP(S_m; dl') + T(S_m; u(l'), dS_m) + gam D^2 C(S_m) dS_m]
+          dl = dl' + dm + VJP(S; dt/4 dl' + h dm) + T(S; u(c), dS) + dt/4 gam D^2 C(S) dS.
+        l and dl run backwards together; only the dS trajectory is stored.  One _lib.ode_hvp pass
+        per stage for all L directions, one VJP per stage and direction.
+        gauss_newton=True: the T, D^2 C and lam K terms are dropped, leaving J^T (Hess data) J d with
+        J = d q_nt / d p0 -- positive semi-definite where the data Hessian is, the usual stand-in
+        where the exact Hessian is indefinite; the regulariser's own (positive definite) part
+        lam K(q0, q0) d is then the caller's to add.
+        The data Hessian, in order of preference: data_hvp(q1, dq1) with dq1 (L, M, D); the
+        attribute dataloss.hvp of the same signature (BasicQuadLossFunctor and DiffPSR's
+        QuadLossFunctor have one); torch double-backward of dataloss, one direction at a time.
+        shoot: a forward shoot of (q0, p0) without carried points whose support states are reused.
+        Inputs are detached; the model (its shoot_cache included) is left as it was.
+        ValueError for eta != 0 (as shoot_tangent), with an active row split (the second-order
+        pass has no split form), for a shoot with carried points (the loss of an external x0 is
+        not covered) and for a direction of the wrong shape."""
+        if self.eta != 0:
+            raise ValueError("loss_hvp needs eta = 0 (gradcomponent=False): the second-order operator is that "
+                             "of the Hamiltonian without the gradient component")
+        if self._split() is not None:
+            raise ValueError("loss_hvp: not available with an active row split")
+        if shoot is not None and getattr(shoot, "X", None) is not None:
+            raise ValueError("loss_hvp: the shoot carries points x0; only the loss on the support points "
+                             "(Optimize with x0=None) is covered")
+        getspec(q0, p0, d)
+        q0, p0, d = q0.detach().contiguous(), p0.detach().contiguous(), d.detach()
+        single = d.dim() == 2
+        dd = (d[None] if single else d).contiguous()
+        if dd.dim() != 3 or tuple(dd.shape[1:]) != tuple(q0.shape) or p0.shape != q0.shape:
+            raise ValueError(f"loss_hvp: d must be shaped {tuple(q0.shape)} or (L, {q0.shape[0]}, "
+                             f"{q0.shape[1]}), got {tuple(d.shape)}")
+        L = dd.shape[0]
+        if shoot is None:
+            Q, P = self._support_states(q0, p0)
+        else:
+            Q, P = shoot.Q.detach(), shoot.P.detach()
+        nt = Q.shape[0] - 1
+        sigma, dt = self.Kernel.sigma, 1.0 / nt
+        h = 2 * dt / 3
+        euler = self.scheme == "Euler"
+        exact = not gauss_newton
+        cost = exact and bool(self.withlogdet)
+        raw = self._raw_for(q0)
+        sh = Shoot(Q, P, None)
+        dQ, dP, _ = self._shoot_tangent(q0, p0, dd, None, None, None, sh, True, True)
+        q1 = Q[nt]
+        if data_hvp is None:
+            data_hvp = getattr(dataloss, "hvp", None)
+        if data_hvp is None:
+            data_hvp = lambda x, dx: _autograd_data_hvp(dataloss, x, dx)
+        dlq = data_hvp(q1, dQ[nt]).detach()
+        if tuple(dlq.shape) != tuple(dd.shape):
+            raise ValueError(f"loss_hvp: the data Hessian must be shaped {tuple(dd.shape)}, got {tuple(dlq.shape)}")
+        dlp = torch.zeros_like(dd)
+        gdiv = lambda k: torch.full((1,), k, device=q0.device, dtype=q0.dtype) if cost else None
+        bwd = lambda q, p, gq, gp, g=None: _lib.ode_self_bwd(q, p, gq.contiguous(), gp.contiguous(), g, sigma, 0.0)
+
+        def bwd_dirs(q, p, gq, gp):          # VJP(S; .) of each direction
+            outs = [bwd(q, p, gq[l], gp[l]) for l in range(L)]
+            if not outs:
+                return torch.zeros_like(dd), torch.zeros_like(dd)
+            return torch.stack([o[0] for o in outs]), torch.stack([o[1] for o in outs])
+
+        with torch.no_grad(), _lib.coord_mode(raw):
+            if exact:
+                lq, lp = _data_grad(dataloss, q1), torch.zeros_like(q1)
+            for t in range(nt - 1, -1, -1):
+                q, p = Q[t], P[t]
+                dq, dp = dQ[t], dP[t]
+                if euler:
+                    gq, gp = bwd_dirs(q, p, dlq, dlp)
+                    if exact:
+                        tq, tp = _lib.ode_hvp(q, p, -lp, lq, dq, dp, sigma, gdiv(1.0))
+                        gq, gp = gq + tq, gp + tp
+                        aq, ap = bwd(q, p, lq, lp, gdiv(1.0))
+                        lq, lp = lq + dt * aq, lp + dt * ap
+                    dlq, dlp = dlq + dt * gq, dlp + dt * gp
+                    continue
+                vq, mG = _lib.ode_self_fwd(q, p, sigma, 0.0, False)[:2]
+                qm, pm = q + h * vq, p + h * mG
+                dmq, dmp = bwd_dirs(qm, pm, dlq, dlp)
+                if exact:
+                    dv1, dG1, _ = _lib.ode_tlm(q, p, dq, dp, sigma)
+                    tq, tp = _lib.ode_hvp(qm, pm, -lp, lq, dq + h * dv1, dp + h * dG1, sigma, gdiv(1.0))
+                    dmq, dmp = dmq + tq, dmp + tp
+                dmq, dmp = (0.75 * dt) * dmq, (0.75 * dt) * dmp
+                gq, gp = bwd_dirs(q, p, (0.25 * dt) * dlq + h * dmq, (0.25 * dt) * dlp + h * dmp)
+                if exact:
+                    mq, mp = bwd(qm, pm, lq, lp, gdiv(1.0))
+                    mq, mp = (0.75 * dt) * mq, (0.75 * dt) * mp
+                    cq, cp = (0.25 * dt) * lq + h * mq, (0.25 * dt) * lp + h * mp
+                    tq, tp = _lib.ode_hvp(q, p, -cp, cq, dq, dp, sigma, gdiv(0.25 * dt))
+                    gq, gp = gq + tq, gp + tp
+                    aq, ap = bwd(q, p, cq, cp, gdiv(0.25 * dt))
+                    lq, lp = lq + mq + aq, lp + mp + ap
+                dlq, dlp = dlq + dmq + gq, dlp + dmp + gp
+            out = dlp
+            if exact and L > 0:
+                out = out + self.lam * torch.stack([self.Kernel.KRed(q0, q0, dd[l]) for l in range(L)])
+        return out[0] if single else out
+
+    def loss_hessian_extremes(self, dataloss, q0, p0, steps, seed=0, gauss_newton=False):
+        """The extreme eigenvalues of the Hessian loss_hvp applies, by `steps` Lanczos iterations
+        with full reorthogonalisation (tools/lanczos.py; one loss_hvp per iteration, the small
+        tridiagonal algebra in float64 on the host) from a random start drawn with `seed`.
+        Returns (ritz, vmin, vmax): the Ritz values in ascending order (float64, on the host; as
+        many as iterations ran -- fewer than `steps` on an invariant subspace) and the unit Ritz
+        vectors of the smallest and the largest, shaped like p0.  ritz[0] < 0 shows a direction of
+        negative curvature; ritz[-1] / ritz[0] estimates the conditioning from below."""
+        from ..tools.lanczos import lanczos
+        q0, p0 = q0.detach(), p0.detach()
+        sh = Shoot(*self._support_states(q0, p0), None)
+        matvec = lambda v: self.loss_hvp(dataloss, q0, p0, v.reshape(p0.shape), gauss_newton=gauss_newton,
+                                         shoot=sh).reshape(-1)
+        g = torch.Generator().manual_seed(int(seed))
+        v0 = torch.randn(p0.numel(), generator=g, dtype=torch.float64).to(device=p0.device, dtype=p0.dtype)
+        ritz, vecs = lanczos(matvec, v0, int(steps))
+        return ritz, vecs[0].reshape(p0.shape), vecs[-1].reshape(p0.shape)
+
     def BasicQuadLossFunctor(self, y, cmul=1):
         y = y.detach()
 
         def dataloss(x):
             return ((x - y) ** 2).sum() * cmul / 2
+        dataloss.hvp = lambda x, dx: cmul * dx     # loss_hvp: the Hessian is cmul I
         return dataloss
 
     def trajloss(self, shoot):

@@ -421,7 +421,20 @@ class DiffPSR(MultiPSR):
             d = x - y
             return (d ** 2 / s2x).sum(), inv * (2.0 * d)
         dataloss_func.value_and_grad = value_and_grad
+        # LDDMMModel.loss_hvp: the Hessian is diag(1 / sigma_s^2)
+        dataloss_func.hvp = lambda x, dx: (2.0 * inv) * dx
         return dataloss_func
+
+    def frame_hvp(self, k, d, gauss_newton=False):
+        """The Hessian-vector product (LDDMMModel.loss_hvp) of the loss Reg_opt minimises for frame
+        k -- lam H + cost + QuadLossFunctor(k) on the shot support points -- at the current a0[k],
+        along d, (M, D) or (L, M, D).  Only for the dense support scheme (every data point a support
+        point): with a decimated or grid support the data term reads carried points, which
+        loss_hvp does not cover (ValueError)."""
+        if self.support_scheme is not None:
+            raise ValueError(f"frame_hvp needs the dense support scheme, not {self.support_scheme!r}: the data "
+                             "term of a carried point set is not covered by loss_hvp")
+        return self.LMi.loss_hvp(self.QuadLossFunctor(k), self.q0[k], self.a0[k], d, gauss_newton=gauss_newton)
 
     def _optimize_frame(self, k, nmax, tol):
         if self.support_scheme is None:

@@ -24,6 +24,8 @@ size_t dicp_gram_ws(int64_t M, int64_t N, int D);
 int dicp_gram_splits(int64_t M, int64_t N);
 size_t dicp_tlm_ws(int64_t M, int64_t N, int D);
 int dicp_tlm_splits(int64_t M, int64_t N);
+size_t dicp_hvp_ws(int64_t M, int64_t N, int D);
+int dicp_hvp_splits(int64_t M, int64_t N);
 
 namespace {
 thread_local char g_err[512] = "";
@@ -67,6 +69,8 @@ extern "C" size_t dicp_workspace_bytes(int kind, int64_t M, int64_t N, int D) {
     b = dicp_gram_ws(M, N, D);
   else if (kind == DICP_WS_ODE_TLM)
     b = dicp_tlm_ws(M, N, D);
+  else if (kind == DICP_WS_ODE_HVP)
+    b = dicp_hvp_ws(M, N, D);
   else if (kind == DICP_WS_ODE_EXT_JAC)
     b = dicp_ext_jac_ws(M, N, D);
   else if (kind == DICP_WS_ODE_EXT_INV)
@@ -86,6 +90,7 @@ extern "C" int dicp_num_splits(int kind, int64_t M, int64_t N) {
   if (kind == DICP_WS_GMM_CARRY) return dicp_carry_splits(M, N);
   if (kind == DICP_WS_RKHS_GRAM) return dicp_gram_splits(M, N);
   if (kind == DICP_WS_ODE_TLM) return dicp_tlm_splits(M, N);
+  if (kind == DICP_WS_ODE_HVP) return dicp_hvp_splits(M, N);
   // the Newton step's pair pass is the velocity-gradient pass itself
   if (kind == DICP_WS_ODE_EXT_JAC || kind == DICP_WS_ODE_EXT_INV) return dicp_ext_jac_splits(M, N);
   return dicp_lddmm_splits(kind, M, N);

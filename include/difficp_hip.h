@@ -203,6 +203,37 @@ int dicp_lddmm_ode_tlm_f32(const float* q, const float* p, const float* dq, cons
                            double sigma, float* dv, float* dmG, float* dvx, void* ws,
                            size_t ws_bytes, dicp_stream_t stream);
 
+/* Second-order operator of the eta = 0 ODE (no reference counterpart): what a Hessian-vector
+ * product of a shooting loss needs beside the VJP and the tangent-linear model.  With
+ * H(q, p) = 1/2 sum_ij K_ij p_i.p_j, the VJP and the TLM are D^2 H(S)[a, .]; this is
+ * T(S; a, b) = grad_S (D^2 H(S)[a, b]), symmetric in (a, b), for one direction a = (aq, ap) (M, D)
+ * and L directions b_l = (bq, bp) (L, M, D), contiguous, which share (q, p, aq, ap).  With
+ * s = 1/sigma^2, z = q_i - q_j, K = exp(-s |z|^2 / 2), alpha = aq_i - aq_j, beta = bq_i - bq_j,
+ *   P = p_i.p_j, P_a = ap_i.p_j + p_i.ap_j, P_b = bp_i.p_j + p_i.bp_j, P_ab = ap_i.bp_j + bp_i.ap_j,
+ *   A = s^2 (z.alpha)(z.beta) - s (alpha.beta), c = A P - s (z.alpha) P_b - s (z.beta) P_a + P_ab:
+ *     T_p,i = sum_j K { A p_j - s (z.alpha) bp_j - s (z.beta) ap_j }
+ *     T_q,i = sum_j K { -s c z + [s^2 (z.beta) P - s P_b] alpha + [s^2 (z.alpha) P - s P_a] beta }
+ * gdiv (device scalar, may be NULL = the terms are not evaluated) adds gdiv D^2 C(S) b_l, the
+ * Hessian-vector product of the divergence sum C = s sum_ij K (z.p_j) (the cost channel whose
+ * cotangent dicp_lddmm_ode_self_bwd_f32 takes as gdiv); with u = p_i - p_j, du = bp_i - bp_j:
+ *     (D^2 C b)_p,i = s sum_j K [ s (z.beta) z - beta ]
+ *     (D^2 C b)_q,i = s sum_j K { -s [s (z.beta)(z.u) - beta.u - z.du] z + s (z.u) beta
+ *                                 + s (z.beta) u - du }
+ * into out_q, out_p (L, M, D) (either may be NULL).  One pair launch for all L directions (the
+ * direction is a grid dimension) and, where the support is split into column chunks, one merge
+ * launch; no atomics.  The result of direction l is bitwise reproducible and depends on
+ * (q, p, aq, ap), that direction's (bq, bp), gdiv and M only -- not on L, the other directions,
+ * the device or any option.  Coordinates in original units; one v_exp_f32 per pair; float32 sums
+ * over 256-column tiles, then tiles, then chunks in order.  D = 2 or 3 (otherwise
+ * DICP_ERR_UNSUPPORTED).  M or L negative, L > 65535, sigma <= 0, a NULL input, an output that is
+ * an input: DICP_ERR_INVALID, before any device work.  M = 0 or L = 0 launches nothing.
+ * Workspace kind DICP_WS_ODE_HVP: dicp_workspace_bytes answers for ONE direction, a call needs
+ * L times that.  Not batchable. */
+int dicp_lddmm_ode_hvp_f32(const float* q, const float* p, const float* aq, const float* ap,
+                           const float* bq, const float* bp, int64_t M, int L, int D,
+                           double sigma, const float* gdiv, float* out_q, float* out_p, void* ws,
+                           size_t ws_bytes, dicp_stream_t stream);
+
 /* VJP of the external-point terms.  Cotangents gvx (N,D) on vx and device scalar gdiv on
  * sum_i gx_i.  Writes gxo (N,D) (gradient w.r.t. x) and ACCUMULATES into gq, gp (M,D)
  * (gradient w.r.t. the support points / momenta), so it can follow the self backward. */
@@ -542,8 +573,10 @@ enum dicp_ws_kind {
                                     the slabs of DICP_WS_ODE_EXT_JAC and N (D + D^2) floats of scratch */
   DICP_WS_GMM_CARRY = 16,        /* dicp_gmm_carry_f32: M = rows, N = columns */
   DICP_WS_RKHS_GRAM = 17,        /* dicp_rkhs_gram_f32: M = max_rows, N = npairs */
-  DICP_WS_ODE_TLM = 18           /* dicp_lddmm_ode_tlm_f32: M = support points, N = carried points; the
+  DICP_WS_ODE_TLM = 18,          /* dicp_lddmm_ode_tlm_f32: M = support points, N = carried points; the
                                     bytes of ONE direction (a call needs L times as many) */
+  DICP_WS_ODE_HVP = 19           /* dicp_lddmm_ode_hvp_f32: M = support points, N unused; the bytes of
+                                    ONE direction (a call needs L times as many) */
 };
 size_t dicp_workspace_bytes(int kind, int64_t M, int64_t N, int D);
 
